@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the DeepAVFusion/AVMAE pre-training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config base|base_m75|base_as|large]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config base|base_m75|base_as|large] [--full] [--dump-outputs DIR]
 
 One "step" = bf16 weight refresh + forward + backward + (DP gradient all-reduce) + global grad norm + AdamW
 on one synthetic batch (B AV pairs per GPU) resident in HBM.  Prints ONE JSON line on rank 0.
 For N > 1 the driver launches this file with torch.distributed.run (one rank per GPU, RCCL).
+A plain run sets up, warms up, times the K steps and prints the headline figure.  --full adds everything else this file
+measures behind the timed region: the audio-mask-0.75 variant, the rooflines of the dominant kernels, the data-parallel
+communication figures and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -101,6 +104,31 @@ def _spawn_ranks(n):
     return max(abs(rc) for rc in rcs)
 
 
+DUMP_SAMPLE = 1 << 20       # entries per optimizer-state buffer in --dump-outputs (3 x 4 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, out, opt):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy — what the step returns (loss_image,
+    loss_audio and, for the captured step, the global gradient norm) and the state it leaves behind: a fixed, seeded sample
+    (DUMP_SAMPLE entries, the same indices in every run) of the fp32 master weights and of both AdamW moments.  main() starts
+    that step from the seeded initial weights and zero moments, so that its inputs are the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(('loss_image', 'loss_audio', 'grad_norm'), out))
+    flat_p = opt.flat.flat_p
+    n = flat_p.numel()
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n, device=flat_p.device)
+    else:
+        gen = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=gen).sort().values.to(flat_p.device)
+    for name, buf in (('params', flat_p), ('adam_exp_avg', opt.exp_avg), ('adam_exp_avg_sq', opt.exp_avg_sq)):
+        arrays[name + '_sample'] = buf[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -109,14 +137,24 @@ def main():
     ap.add_argument('--batch', type=int, default=0, help='AV pairs per GPU (default: 64 ViT-B, 32 ViT-L)')
     ap.add_argument('--config', default='base')
     ap.add_argument('--no-graph', action='store_true', help='eager kernel launches instead of hipGraph replay')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the audio-mask-0.75 variant, the kernel rooflines, the data-parallel '
+                         'communication figures and the CPU baseline (a plain run prints the headline figure only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32; losses, grad norm, seeded samples '
+                         'of the weights and AdamW moments); that step starts from the initial weights and zero moments, so it '
+                         'repeats from run to run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the cpu_baseline leg')
     ap.add_argument('--cpu-threads', type=int, default=0,
-                    help='host threads for the cpu_baseline leg (0 = min(16, cores): more threads oversubscribe these matmuls — '
+                    help='host threads for the cpu_baseline leg of --full (0 = min(16, cores): more threads oversubscribe these matmuls — '
                          '128 threads are 7x slower than 16 on the MI355X host; 1 = scalar figure)')
-    ap.add_argument('--no-roofline', action='store_true', help='skip the dominant-kernel replay (clean per-step profiles)')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the kernel replays (rooflines)')
     ap.add_argument('--roofline-only', action='store_true',
-                    help='one eager step (to record the launch mix) + 20 replays of the dominant kernel: the run profiled for profiles/*roofline*')
+                    help='one eager step (to record the launch mix) + 20 replays of the dominant kernel: the run profiled for profiles/*roofline* (implies --full)')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    full = a.full or a.roofline_only
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -163,6 +201,20 @@ def main():
     lr = 1.5e-4 * B * world / 256                                                              # train.py:32-34
     opt = FlatAdamW(groups, lr=lr, betas=(0.9, 0.95), model=model)
     trainer = Trainer(model, optimizer=opt, accum_iter=1, use_amp=True, distributed=world > 1 or force_dist)
+    reset_state = None
+    if a.dump_outputs:
+        # A chain of training steps does not repeat bit for bit: the split-K weight gradients and the mask tokens' gradients are
+        # summed with fp32 atomics, and the bf16 weight mirror turns their last-bit differences into whole bf16 steps within a
+        # few updates.  The dumped (last timed) step therefore starts from the seeded initial weights and zero AdamW moments:
+        # its inputs are the same in every run, and what it computes from them repeats to rounding.
+        p_init = opt.flat.flat_p.clone()
+
+        def reset_state():
+            opt.flat.flat_p.copy_(p_init)
+            opt.exp_avg.zero_()
+            opt.exp_avg_sq.zero_()
+            opt.flat.zero_grad()
+            opt.sync_bf16()
     g = torch.Generator(device=dev)
     g.manual_seed(1234 + rank)
     image = torch.randn(B, 3, *cfg.image_size, device=dev, generator=g)
@@ -170,9 +222,11 @@ def main():
     torch.manual_seed(0 + rank)                            # masking noise stream, per rank (util/distributed.py:90-94)
 
     # ---- record the launch mix of ONE step (rank 0): NT launches as the library really issues them (grouped or single,
-    # from the library's own issue log), the grouped weight-gradient launches and the attention calls ------------------
+    # from the library's own issue log), the grouped weight-gradient launches and the attention calls.  Recorded for the
+    # rooflines of --full and for DAV_DUMP_MIX only; the eager step itself runs in every run (the first warm-up pass) ----
     tn_log, attn_log = [], []
-    if rank == 0:
+    record_mix = rank == 0 and (full or bool(os.environ.get('DAV_DUMP_MIX')))
+    if record_mix:
         orig_tn, orig_tg, orig_af, orig_ab = ops.gemm_tn_grouped, ops.gemm_tn_gang, ops.attn_fwd, ops.attn_bwd
 
         def log_tn(problems):
@@ -200,7 +254,7 @@ def main():
         return li, la
     eager_step()                          # every rank (collectives inside); also the first warm-up pass
     nt_log = []
-    if rank == 0:
+    if record_mix:
         nt_log = ops.nt_issue_log()
         ops.nt_issue_log(False)
         ops.gemm_tn_grouped, ops.gemm_tn_gang, ops.attn_fwd, ops.attn_bwd = orig_tn, orig_tg, orig_af, orig_ab
@@ -223,16 +277,28 @@ def main():
         if world > 1 or force_dist:
             torch.distributed.barrier()
             torch.cuda.synchronize()
+
+    def timed(n):
+        """n steps back to back -> (host seconds to the synchronise after the last one, device-event ms of every step, what the last returned)"""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
+        t0 = time.perf_counter()
+        ev[0].record()
+        for i in range(n):
+            out = step()
+            ev[i + 1].record()
+        sync()
+        return time.perf_counter() - t0, [ev[i].elapsed_time(ev[i + 1]) for i in range(n)], out
+
     sync()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    t0 = time.perf_counter()
-    ev[0].record()
-    for i in range(a.steps):
-        out = step()
-        ev[i + 1].record()
-    sync()
-    dt = time.perf_counter() - t0
-    step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps))       # device-event time per step
+    if reset_state is None:
+        dt, step_ms, out = timed(a.steps)
+    else:                                  # --dump-outputs: the last timed step starts from the initial state (outside the clock)
+        dt, step_ms, out = timed(a.steps - 1) if a.steps > 1 else (0.0, [], None)
+        reset_state()
+        sync()
+        dt_last, ms_last, out = timed(1)
+        dt, step_ms = dt + dt_last, step_ms + ms_last
+    step_ms = sorted(step_ms)                    # device-event time per step (BASELINE.md section 4)
     median_ms = step_ms[len(step_ms) // 2]
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -241,11 +307,13 @@ def main():
     loss = float(out[0]) + float(out[1])
     ms = dt / a.steps * 1e3
     pairs_per_s = B * world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, opt)
     # ---- data-parallel runs: what the collectives cost the step.  The same captured step is replayed with the reducer's whole
     # schedule intact but NO collective issued (GradReducer.skip_collectives): comm_ms_exposed = step time - that.  After the
     # timed region; ranks train on un-averaged gradients meanwhile, which nothing reads any more. -------------------------------
     comm = None
-    if (world > 1 or force_dist) and not (a.no_graph or a.roofline_only):
+    if full and (world > 1 or force_dist) and not (a.no_graph or a.roofline_only):
         red = trainer.model.reducer
         red.skip_collectives = True
         for _ in range(2):
@@ -315,7 +383,7 @@ def main():
 
     # ---- BASELINE.md section 4 asks for the audio-mask-0.75 variant beside the default 0.8 (80 instead of 63 kept audio
     # tokens): same model and optimizer, a second captured step, a short timed run; labelled secondary -----------------
-    if world == 1 and not (a.no_graph or a.roofline_only) and abs(cfg.audio_mask_ratio - 0.8) < 1e-9:
+    if full and world == 1 and not (a.no_graph or a.roofline_only) and abs(cfg.audio_mask_ratio - 0.8) < 1e-9:
         model.audio_mask_ratio = 0.75
         gs75 = GraphedStep(trainer, image.shape, audio.shape)
         for _ in range(3):
@@ -373,7 +441,7 @@ def main():
     def t128(probs):
         return sum(((M + 127) // 128) * ((N + 127) // 128) for (M, N, K) in probs)
     big = [(cfg_id, bt, probs) for (cfg_id, bt, probs) in nt_log if t128(probs) >= BIG_LAUNCH_TILES]
-    if big and not a.no_roofline:
+    if full and big and not a.no_roofline:
         bufs = {}
         for _c, bt, probs in big:
             for (M, N, K) in probs:
@@ -514,7 +582,7 @@ def main():
     # ---- weight-gradient kernels: the step's launches as the engine issued them — the gang-scheduled 256 x 256 launch(es)
     # (gemm_tn_gang_kernel: both decoders, then all encoder layers of a captured segment) and whatever small flushes stayed on the
     # 128 x 128 grouped kernel.  Operands are shared per shape (read only), every problem has its own gradient buffer.
-    if tn_log and not a.no_roofline:
+    if full and tn_log and not a.no_roofline:
         tbufs, launches = {}, []
         for kind, probs in tn_log:
             plist = []
@@ -554,7 +622,7 @@ def main():
                                     'note': 'isolated replay of the recorded launches on fresh operands, written (not accumulated) tiles as in the captured step'}
         del tbufs, launches
     # ---- attention family (isolated replays of the step's shapes; in the step equal-rank calls of both towers are one grid)
-    if attn_log and not a.no_roofline:
+    if full and attn_log and not a.no_roofline:
         classes = {}
         for (kind, B_, H, Nq, Nk, dqk, dv) in attn_log:
             classes.setdefault((B_, H, Nq, Nk, dqk, dv), {'fwd': 0, 'bwd': 0})[kind] += 1
@@ -611,7 +679,7 @@ def main():
                                         'shapes': entries}
 
     # ---- CPU baseline: the fp32 oracle (a port of the reference's path) on this box's host cores ---------------
-    if world == 1 and not a.no_cpu_baseline:
+    if full and world == 1 and not a.no_cpu_baseline:
         from oracle import avmae_oracle as O
         from oracle.configs import CONFIGS as OC
         ocfg = OC[a.config]

@@ -431,6 +431,32 @@ def test_bench_starts_its_own_ranks_when_launched_plainly():
     assert d['dry'] and d['world'] == 4 and d['rank'] == 0 and d['master'] == '127.0.0.1' and d['port'] > 0 and d['argv_gpus'] == 4
 
 
+def test_bench_dump_outputs_are_float32_seeded_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's return values and a sample of the optimizer state it leaves, as float32
+    .npy files; the sample takes the same entries in every run (two builds compare output for output), 64 MB at most in all."""
+    import types
+    import bench
+    n = 3 * bench.DUMP_SAMPLE
+    g = torch.Generator().manual_seed(0)
+    opt = types.SimpleNamespace(flat=types.SimpleNamespace(flat_p=torch.randn(n, generator=g)),
+                                exp_avg=torch.randn(n, generator=g), exp_avg_sq=torch.rand(n, generator=g))
+    out = (torch.tensor(1.5), torch.tensor(2.5), torch.tensor([0.25]))
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), out, opt)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['adam_exp_avg_sample.npy', 'adam_exp_avg_sq_sample.npy', 'grad_norm.npy', 'loss_audio.npy', 'loss_image.npy',
+                     'params_sample.npy']
+    total = 0
+    for f in names:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / 'a' / 'loss_audio.npy')) == 2.5
+    p = np.load(tmp_path / 'a' / 'params_sample.npy')
+    assert p.size == bench.DUMP_SAMPLE and np.isin(p, opt.flat.flat_p.numpy()).all()
+
+
 def _asm_first_readers(asm_text):
     """-> (checked, offenders): inline-asm VALU instructions that read a register of the most recent (program order) MFMA result
     with NO compiler-visible VALU reader of that same result earlier IN THE SAME BASIC BLOCK.  The compiler pads ITS OWN first

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/profiles_$R
 mkdir -p $OUT
 # 1. default bench under --kernel-trace --stats
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --full --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench.err
 cp $(find $OUT/bench -name "*kernel_stats.csv" | head -1) $OUT/${R}_bench_kernel_stats.csv
 # 2. dominant-kernel replay only
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/roof -o roof -- python3 bench.py --roofline-only > $OUT/${R}_roofline_bench.json 2> $OUT/roof.err

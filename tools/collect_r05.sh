@@ -6,9 +6,9 @@ OUT=gpurun_out/r05; mkdir -p $OUT
 # 1. the GPU suite as the driver runs it
 if [ "$1" != "quick" ]; then timeout 2400 python -m pytest tests -x -q -m gpu --durations=12 > $OUT/r05_gputest.log 2>&1; tail -3 $OUT/r05_gputest.log; fi
 # 2. bench lines: BASELINE configs[1] (default), configs[2] shapes, configs[3] ViT-L, configs[4] video
-timeout 900 python bench.py > $OUT/r05_bench.json 2> $OUT/bench.err
-timeout 900 python bench.py --config base_as --no-cpu-baseline > $OUT/r05_bench_base_as.json 2> $OUT/bench_as.err
-timeout 900 python bench.py --config large --no-cpu-baseline > $OUT/r05_bench_large.json 2> $OUT/bench_l.err
+timeout 900 python bench.py --full > $OUT/r05_bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --config base_as --no-cpu-baseline > $OUT/r05_bench_base_as.json 2> $OUT/bench_as.err
+timeout 900 python bench.py --full --config large --no-cpu-baseline > $OUT/r05_bench_large.json 2> $OUT/bench_l.err
 timeout 600 python tools/video_bench.py > $OUT/r05_bench_video.json 2> $OUT/bench_v.err
 # 3. rocprofv3 summaries: the captured step in situ (graph replays; per-kernel averages = in-step durations) and the roofline replay
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --no-cpu-baseline --no-roofline --steps 20 --warmup 3 > $OUT/r05_bench_profiled.json 2> $OUT/prof.err

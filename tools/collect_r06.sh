@@ -8,9 +8,9 @@ echo "$DAV_MEASURED_ON" > $OUT/measured_on.txt
 # 1. the GPU suite as the driver runs it
 if [ "$1" != "quick" ]; then timeout 2400 python -m pytest tests -x -q -m gpu --durations=12 > $OUT/r06_gputest.log 2>&1; tail -3 $OUT/r06_gputest.log; fi
 # 2. bench lines: BASELINE configs[1] (default), configs[2] shapes, configs[3] ViT-L, configs[4] video
-timeout 900 python bench.py > $OUT/r06_bench.json 2> $OUT/bench.err
-timeout 900 python bench.py --config base_as --no-cpu-baseline > $OUT/r06_bench_base_as.json 2> $OUT/bench_as.err
-timeout 900 python bench.py --config large --no-cpu-baseline > $OUT/r06_bench_large.json 2> $OUT/bench_l.err
+timeout 900 python bench.py --full > $OUT/r06_bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --config base_as --no-cpu-baseline > $OUT/r06_bench_base_as.json 2> $OUT/bench_as.err
+timeout 900 python bench.py --full --config large --no-cpu-baseline > $OUT/r06_bench_large.json 2> $OUT/bench_l.err
 timeout 600 python tools/video_bench.py > $OUT/r06_bench_video.json 2> $OUT/bench_v.err
 # 3. rocprofv3 summaries: the captured step in situ and the roofline replay
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --no-cpu-baseline --no-roofline --steps 20 --warmup 3 > $OUT/r06_bench_profiled.json 2> $OUT/prof.err
@@ -47,7 +47,7 @@ bash tools/ab_env2.sh "DAV_LN_FUSE=0" "DAV_LN_FUSE=1" > $OUT/r06_ln_fuse_ab.txt 
 bash tools/runs_r06/phases_ab.sh DAV_LN_FUSE=0 DAV_LN_FUSE=1 > $OUT/r06_ln_phases.txt 2>&1
 python3 tools/runs_r06/fwd_only.py > $OUT/r06_ln_fwd_only.txt 2>&1
 # 6. single-rank cost of the data-parallel machinery
-DAV_FORCE_DIST=1 timeout 600 python bench.py --no-cpu-baseline --no-roofline --steps 40 > $OUT/r06_bench_dp1.json 2> $OUT/dp1.err
+DAV_FORCE_DIST=1 timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --steps 40 > $OUT/r06_bench_dp1.json 2> $OUT/dp1.err
 bash tools/runs_r06/dp1_tax.sh > $OUT/r06_dp1_tax.txt 2>&1
 # 7. ViT-L (configs[3]): phases / concurrency / families of its step, launch-batch policy A/B
 bash tools/runs_r06/large_probe.sh > /dev/null 2>&1
