@@ -605,7 +605,9 @@ extern "C" int dav_dropout_rows(const void* in, int in_f32, const float* res, co
   if (B <= 0 || rows <= 0 || D <= 0 || (D & 3)) return DAV_ERR_SHAPE;
   if (!in || !out) return DAV_ERR_SHAPE;
   if (keep && !(keep_scale > 0.f)) return DAV_ERR_SHAPE;
-  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)res) & 7 || ((uintptr_t)keep & 3)) return DAV_ERR_ALIGN;
+  // four elements per access: float4 for res and fp32 in / out (16 bytes), 8 bytes for bf16 in / out, uchar4 for keep
+  if (((uintptr_t)in & (in_f32 ? 15 : 7)) || ((uintptr_t)out & (out_f32 ? 15 : 7)) || ((uintptr_t)res & 15) || ((uintptr_t)keep & 3))
+    return DAV_ERR_ALIGN;
   const dim3 grid(wave_grid((long)B * rows)), block(256);
   const unsigned char* kp = (const unsigned char*)keep;
   if (in_f32 && out_f32) { DAV_LAUNCH((dropout_rows_kernel<true, true>), grid, block, 0, stream, in, res, kp, keep_scale, rowscale, B, rows, D, out); }

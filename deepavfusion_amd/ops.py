@@ -254,9 +254,10 @@ def _tn_problem_array(problems):
     return arr
 
 
-def gemm_tn_gang(problems):
+def gemm_tn_gang(problems, workspace_fill=None):
     """The queued weight-gradient problems of several layers (dicts as for gemm_tn_grouped, no two with the same C) as ONE
-    gang-scheduled launch of 256 x 256 tiles (dav_gemm_tn_gang_bf16).  The workspace is allocated here on the current stream."""
+    gang-scheduled launch of 256 x 256 tiles (dav_gemm_tn_gang_bf16).  The workspace is allocated here on the current stream
+    (``workspace_fill``: a byte value to fill it with first — tests check that the kernel initialises its own state)."""
     if not problems:
         return
     if problems[0]['A'].dtype == F32:
@@ -267,6 +268,8 @@ def gemm_tn_gang(problems):
     if nbytes == 0:
         raise RuntimeError('dav_gemm_tn_gang_workspace_bytes: invalid weight-gradient problem (shape / alignment)')
     ws = torch.empty(nbytes, dtype=torch.uint8, device=problems[0]['A'].device)
+    if workspace_fill is not None:
+        ws.fill_(workspace_fill)
     hold(ws)
     _lib.check(lib.dav_gemm_tn_gang_bf16(arr, len(problems), _ptr(ws), nbytes, _stream()), 'dav_gemm_tn_gang_bf16')
 

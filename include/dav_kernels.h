@@ -290,7 +290,7 @@ int dav_rows_scale_cast(const float* g, const float* scale, int B, int rows, int
 /* Dropout on activations (timm Mlp.drop1 / drop2, the attention modules' proj_drop; fine-tuning constructors' drop > 0), DropPath
  * folded in: out[b,r,:] = (res ? res[b,r,:] : 0) + (rowscale ? rowscale[b] : 1) * (keep[b,r,:] ? keep_scale : 0) * in[b,r,:].
  * keep: bytes 0 / 1 [B*rows][D] (null = all kept), in / out bf16 (in_f32 / out_f32 = 0) or fp32 (1), D % 4 == 0; out may alias
- * in or res.  The backward is the same call on the gradient (res = null). */
+ * in or res.  Alignment: res and fp32 in / out 16 bytes, bf16 in / out 8 bytes, keep 4 bytes (else DAV_ERR_ALIGN).  The backward is the same call on the gradient (res = null). */
 int dav_dropout_rows(const void* in, int in_f32, const float* res, const void* keep, float keep_scale, const float* rowscale,
                      int B, int rows, int D, void* out, int out_f32, hipStream_t stream);
 /* dpos[r] += sum_b dx[b, off+r]; dmask_token += sum over masked (b, r) */

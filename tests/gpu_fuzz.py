@@ -11,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from deepavfusion_amd import ops   # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import kcheck as kc  # noqa: E402
+
 dev = torch.device('cuda')
 BF16, F32 = torch.bfloat16, torch.float32
 FAILS = []
@@ -28,6 +31,30 @@ def check(tag, err, tol):
     if not (err <= tol):
         FAILS.append((tag, err, tol))
         print(f'FAIL {tag}: {err:.3e} > {tol:.1e}', flush=True)
+
+
+def elem(tag, family, got, ref, bound):
+    """elementwise |got - ref| <= bound (tests/kcheck.py)"""
+    ok, ratio, msg = kc.within(got, ref, bound, tag)
+    kc.note(family, ratio)
+    if not ok:
+        FAILS.append((tag + ' elementwise', ratio, 1.0))
+        print(f'FAIL {msg}', flush=True)
+
+
+def guard(tag, g):
+    n, where = g.stray()
+    if n:
+        FAILS.append((tag + ' guard', n, 0))
+        print(f'FAIL {tag}: {n} stray elements, first in the {where}', flush=True)
+
+
+def kept(tag, t, value):
+    """memory outside the problem (columns of a wider tensor beyond K) is bit-identical to what was there"""
+    n, i = kc.changed(t, torch.full_like(t, value))
+    if n:
+        FAILS.append((tag + ' untouched', n, 0))
+        print(f'FAIL {tag}: {n} elements changed, first at {kc.tile_of(i, tuple(t.shape))}', flush=True)
 
 
 def fuzz_gemm(rng, n):
@@ -63,25 +90,50 @@ def fuzz_gemm(rng, n):
         C0 = torch.randn(M, N, device=dev)
         if beta:
             v = v + C0
-        C = C0.clone().to(BF16) if c_bf16 else C0.clone()
-        C2 = torch.empty(M, N, device=dev, dtype=BF16) if c2_mode else None
-        ops.gemm_nt(A, Bm, M, N, K, ldb=N if kn else K, bias=bias, act=act, res=res, ldres=N, C_out=C, c_bf16=c_bf16, beta=beta,
-                    alpha=alpha, C2=C2, ldc2=N, c2_mode=c2_mode, variant=(1 << 12) if kn else 0)
+        # the output (and its twin) inside guard bands with a random row stride: prefilled when accumulated, else poisoned
+        gC = kc.Guarded(M, N, BF16 if c_bf16 else F32, ld=N + 8 * rng.choice([0, 0, 1, 5]), device=dev, fill=C0 if beta else 'poison')
+        C = gC.t
+        gC2 = kc.Guarded(M, N, BF16, ld=N + 8 * rng.choice([0, 0, 1, 5]), device=dev) if c2_mode else None
+        C2 = gC2.t if c2_mode else None
+        ops.gemm_nt(A, Bm, M, N, K, ldb=N if kn else K, bias=bias, act=act, res=res, ldres=N, C_out=C, ldc=gC.ld, c_bf16=c_bf16, beta=beta,
+                    alpha=alpha, C2=C2, ldc2=gC2.ld if c2_mode else 0, c2_mode=c2_mode, variant=(1 << 12) if kn else 0)
         tag = f'gemm M{M} N{N} K{K} kn{int(kn)} act{act} res{int(res is not None)} beta{beta} bf{int(c_bf16)} c2{c2_mode} bias{int(bias is not None)}'
         check(tag, rel(C.float(), v), 8e-3 if c_bf16 else 2e-4)
         if c2_mode:
             want = {1: pre, 2: post, 3: v, 4: dgelu}[c2_mode]
             check(tag + ' C2', rel(C2.float(), want), 8e-3)
+        # float64: the same epilogue, and the bound of each stage carried through it
+        p64 = alpha * (A.double() @ W.double().t()) + (bias.double() if bias is not None else 0.0)
+        b_pre = kc.C_GEMM * kc.U32 * K * abs(alpha) * kc.gemm_scale(A, W) + kc.out_round(F32) * p64.abs()
+        pre64, b_post = p64, b_pre
+        if act == 1:
+            d64 = 0.5 * (1 + torch.erf(p64 * 0.5 ** 0.5)) + p64 * torch.exp(-0.5 * p64 * p64) / (2 * 3.141592653589793) ** 0.5
+            p64 = 0.5 * p64 * (1 + torch.erf(p64 * 0.5 ** 0.5))
+            b_post = kc.gelu_bound(b_pre, p64, F32)
+        post64 = p64
+        v64 = p64 + (res.double() if res is not None else 0.0) + (C0.double() if beta else 0.0)
+        b_v = b_post + kc.out_round(F32) * v64.abs()
+        elem(tag, 'fuzz_gemm', C, v64, b_v + kc.out_round(C.dtype) * v64.abs())
+        guard(tag, gC)
+        if c2_mode:
+            w64, wb = {1: (pre64, b_pre), 2: (post64, b_post), 3: (v64, b_v)}.get(c2_mode, (None, None)) if c2_mode != 4 else \
+                (d64, kc.dgelu_bound(b_pre, d64, BF16))
+            elem(tag + ' C2', 'fuzz_gemm', C2, w64, wb + kc.U16 * w64.abs())
+            guard(tag + ' C2', gC2)
         # weight gradient of the same problem
         if N % 8 == 0 and K % 8 == 0:
             dY = torch.randn(M, N, device=dev).to(BF16)
             G0 = torch.randn(N, K, device=dev)
-            G = G0.clone()
+            gG = kc.Guarded(N, K, F32, ld=K + 8 * rng.choice([0, 0, 1, 5]), device=dev, fill=G0)
+            G = gG.t
             bg0 = torch.randn(N, device=dev)
             bg = bg0.clone()
-            ops.gemm_tn(dY, A, M, N, K, G, beta=1, bias_grad=bg)
+            ops.gemm_tn(dY, A, M, N, K, G, ldc=gG.ld, beta=1, bias_grad=bg)
             check(tag + ' wgrad', rel(G, G0 + dY.float().t() @ A.float()), 3e-4)
             check(tag + ' bgrad', rel(bg, bg0 + dY.float().sum(0)), 3e-4)
+            g64 = G0.double() + dY.double().t() @ A.double()
+            elem(tag + ' wgrad', 'fuzz_gemm', G, g64, kc.gemm_bound(dY.t(), A.t(), g64, F32))
+            guard(tag + ' wgrad', gG)
 
 
 def fuzz_attn(rng, n):
@@ -97,8 +149,8 @@ def fuzz_attn(rng, n):
         qf, kf, vf = (t.float().permute(0, 2, 1, 3).requires_grad_(True) for t in (q, k, v))
         s = (qf @ kf.transpose(-2, -1)) * scale
         ref = s.softmax(-1) @ vf
-        O = torch.empty(B * Nq, H * dv, device=dev, dtype=BF16)
-        LSE = torch.empty(B, H, Nq, device=dev)
+        O = kc.poisoned((B * Nq, H * dv), BF16, dev)
+        LSE = kc.poisoned((B, H, Nq), F32, dev)
         st = (Nq * H * dqk, H * dqk, Nk * H * dqk, H * dqk, Nk * H * dv, H * dv)
         ops.attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), O, LSE, B, H, Nq, Nk, dqk, dv, *st, Nq * H * dv, H * dv, scale)
         tag = f'attn B{B} H{H} {Nq}x{Nk} d{dqk}/{dv}'
@@ -106,13 +158,20 @@ def fuzz_attn(rng, n):
         check(tag + ' lse', rel(LSE, torch.logsumexp(s, -1)), 2e-4)
         dO = torch.randn(B * Nq, H * dv, device=dev).to(BF16)
         ref.backward(dO.view(B, Nq, H, dv).permute(0, 2, 1, 3).float())
-        dq, dk, dvv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+        Ok = O.view(B, Nq, H, dv).permute(0, 2, 1, 3)
+        r64 = kc.attn_bounds(qf, kf, vf, dO.view(B, Nq, H, dv).permute(0, 2, 1, 3), Ok, scale)
+        elem(tag + ' fwd', 'fuzz_attn', Ok, r64['O'], r64['bO'])
+        elem(tag + ' lse', 'fuzz_attn', LSE, r64['lse'], r64['blse'])
+        dq, dk, dvv = (kc.poisoned(t.shape, BF16, dev) for t in (q, k, v))
         Delta = torch.empty_like(LSE)
         ops.attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), O, dO, LSE, Delta, dq.data_ptr(), dk.data_ptr(), dvv.data_ptr(), B, H, Nq, Nk,
                      dqk, dv, *st, Nq * H * dv, H * dv, Nq * H * dv, H * dv, *st, scale)
         check(tag + ' dq', rel(dq.permute(0, 2, 1, 3).float(), qf.grad), 2.5e-2)
         check(tag + ' dk', rel(dk.permute(0, 2, 1, 3).float(), kf.grad), 2.5e-2)
         check(tag + ' dv', rel(dvv.permute(0, 2, 1, 3).float(), vf.grad), 2.5e-2)
+        elem(tag + ' dq', 'fuzz_attn', dq.permute(0, 2, 1, 3), r64['dq'], r64['bdq'])
+        elem(tag + ' dk', 'fuzz_attn', dk.permute(0, 2, 1, 3), r64['dk'], r64['bdk'])
+        elem(tag + ' dv', 'fuzz_attn', dvv.permute(0, 2, 1, 3), r64['dv'], r64['bdv'])
 
 
 def fuzz_attn_drop(rng, n):
@@ -134,8 +193,8 @@ def fuzz_attn_drop(rng, n):
         qf, kf, vf = (t.float().permute(0, 2, 1, 3).requires_grad_(True) for t in (q, k, v))
         s = (qf @ kf.transpose(-2, -1)) * scale
         ref = (s.softmax(-1) * km) @ vf
-        O = torch.empty(B * Nq, H * dv, device=dev, dtype=BF16)
-        LSE = torch.empty(B, H, Nq, device=dev)
+        O = kc.poisoned((B * Nq, H * dv), BF16, dev)
+        LSE = kc.poisoned((B, H, Nq), F32, dev)
         st = (Nq * H * dqk, H * dqk, Nk * H * dqk, H * dqk, Nk * H * dv, H * dv)
         ops.attn_drop_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), O, LSE, B, H, Nq, Nk, dqk, dv, *st, Nq * H * dv, H * dv, scale,
                           keep, ld, 1.0 / (1.0 - pd))
@@ -144,13 +203,20 @@ def fuzz_attn_drop(rng, n):
         check(tag + ' lse', rel(LSE, torch.logsumexp(s, -1)), 2e-4)
         dO = torch.randn(B * Nq, H * dv, device=dev).to(BF16)
         ref.backward(dO.view(B, Nq, H, dv).permute(0, 2, 1, 3).float())
-        dq, dk, dvv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+        Ok = O.view(B, Nq, H, dv).permute(0, 2, 1, 3)
+        r64 = kc.attn_bounds(qf, kf, vf, dO.view(B, Nq, H, dv).permute(0, 2, 1, 3), Ok, scale, keep=km)
+        elem(tag + ' fwd', 'fuzz_attn_drop', Ok, r64['O'], r64['bO'])
+        elem(tag + ' lse', 'fuzz_attn_drop', LSE, r64['lse'], r64['blse'])
+        dq, dk, dvv = (kc.poisoned(t.shape, BF16, dev) for t in (q, k, v))
         Delta = torch.empty_like(LSE)
         ops.attn_drop_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), O, dO, LSE, Delta, dq.data_ptr(), dk.data_ptr(), dvv.data_ptr(), B, H, Nq, Nk,
                           dqk, dv, *st, Nq * H * dv, H * dv, Nq * H * dv, H * dv, *st, scale, keep, ld, 1.0 / (1.0 - pd))
         check(tag + ' dq', rel(dq.permute(0, 2, 1, 3).float(), qf.grad), 2.5e-2)
         check(tag + ' dk', rel(dk.permute(0, 2, 1, 3).float(), kf.grad), 2.5e-2)
         check(tag + ' dv', rel(dvv.permute(0, 2, 1, 3).float(), vf.grad), 2.5e-2)
+        elem(tag + ' dq', 'fuzz_attn_drop', dq.permute(0, 2, 1, 3), r64['dq'], r64['bdq'])
+        elem(tag + ' dk', 'fuzz_attn_drop', dk.permute(0, 2, 1, 3), r64['dk'], r64['bdk'])
+        elem(tag + ' dv', 'fuzz_attn_drop', dvv.permute(0, 2, 1, 3), r64['dv'], r64['bdv'])
 
 
 def fuzz_ln(rng, n):
@@ -262,7 +328,7 @@ def fuzz_gang(rng, n):
     (mostly ragged), N / K any multiple of 8 (below, across and beyond one 256 x 256 tile), written and accumulated tiles mixed, bias
     gradients on some, row maps (rows-per-batch windows of a taller tensor) on some operands, column blocks of a wider gradient."""
     for it in range(n):
-        probs, refs = [], []
+        probs, refs, guards = [], [], []
         for j in range(rng.choice([1, 1, 2, 3, 5, 8, 13, 24, 24, 45, 90])):      # (> 28 problems: several table-writer launches)
             N = 8 * rng.choice([1, 2, 31, 32, 33, 64, 96, 100, rng.randint(1, 130)])
             K = 8 * rng.choice([1, 3, 32, 33, 64, 65, 96, rng.randint(1, 130)])
@@ -289,16 +355,24 @@ def fuzz_gang(rng, n):
             Cw = torch.full((N, ldc), 0.25, device=dev)
             if ow:
                 Cw[:, :K] = float('nan')
+            guards.append(kc.Guarded(N, ldc, F32, device=dev, fill=Cw))        # the whole (wider) gradient inside guard bands
+            Cw = guards[-1].t
             bg = torch.full((N,), 0.5, device=dev) if rng.random() < 0.4 else None
-            probs.append(dict(A=Af, B=Bf, Mc=Mc, N=N, K=K, C=Cw, lda=N, ldb=K, ldc=ldc, bias_grad=bg, overwrite=ow, **maps))
+            probs.append(dict(A=Af, B=Bf, Mc=Mc, N=N, K=K, C=Cw, lda=N, ldb=K, ldc=ldc, bias_grad=bg, overwrite=ow, As=As, Bs=Bs, **maps))
             ref = torch.full((N, ldc), 0.25, device=dev)
             ref[:, :K] = (0.0 if ow else 0.25) + As.float().t() @ Bs.float()
             refs.append((Cw, ref, bg, None if bg is None else 0.5 + As.float().sum(0), (Mc, N, K, mapped, ow, wide)))
-        ops.gemm_tn_gang(probs)
+        kc.gang(probs)
         for j, (C, rc, bg, rb, what) in enumerate(refs):
             check(f'gang #{it}.{j} {what} C', rel(C, rc), 2e-4)
             if bg is not None:
                 check(f'gang #{it}.{j} {what} bias', rel(bg, rb), 2e-4)
+            pr = probs[j]
+            As, Bs = pr['As'], pr['Bs']
+            r64 = (0.0 if pr['overwrite'] else 0.25) + As.double().t() @ Bs.double()
+            elem(f'gang #{it}.{j} {what} C', 'fuzz_gang', C[:, :pr['K']], r64, kc.gemm_bound(As.t(), Bs.t(), r64, F32))
+            kept(f'gang #{it}.{j} {what} columns beyond K', C[:, pr['K']:], 0.25)
+            guard(f'gang #{it}.{j} {what}', guards[j])
 
 
 if __name__ == '__main__':

@@ -13,6 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from deepavfusion_amd import ops  # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import kcheck as kc  # noqa: E402
+
 dev = torch.device('cuda')
 BF16, F32 = torch.bfloat16, torch.float32
 RESULTS = []
@@ -27,6 +30,28 @@ def report(name, err, tol):
     ok = err <= tol and math.isfinite(err)
     RESULTS.append((name, err, tol, ok))
     print(f'{"PASS" if ok else "FAIL"} {name}: err={err:.3e} tol={tol:.1e}', flush=True)
+
+
+def elem(name, family, got, ref, bound):
+    """elementwise |got - ref| <= bound (tests/kcheck.py); the worst err / bound of each family is kept in kcheck.RATIOS"""
+    ok, ratio, msg = kc.within(got, ref, bound, name)
+    kc.note(family, ratio)
+    RESULTS.append((name + ' elementwise', ratio, 1.0, ok))
+    print(f'{"PASS" if ok else "FAIL"} {name} elementwise: worst err/bound={ratio:.3e}' + (f' — {msg}' if msg else ''), flush=True)
+
+
+def guard(name, g):
+    """every byte around a kcheck.Guarded output (guard bands, row padding) still holds its pattern"""
+    n, where = g.stray()
+    RESULTS.append((name + ' guard', float(n), 0.0, n == 0))
+    print(f'{"PASS" if n == 0 else "FAIL"} {name} guard: {n} stray elements' + (f' — first in the {where}' if n else ''), flush=True)
+
+
+def kept(name, t, before, mask=None):
+    """memory the kernel must not touch (rows a row map skips, context rows, padding) is bit-identical to its snapshot"""
+    n, i = kc.changed(t, before, mask)
+    RESULTS.append((name + ' untouched', float(n), 0.0, n == 0))
+    print(f'{"PASS" if n == 0 else "FAIL"} {name} untouched: {n} elements changed' + (f' — first at {kc.tile_of(i, tuple(t.shape))}' if n else ''), flush=True)
 
 
 def check(fn):
@@ -50,47 +75,70 @@ def rnd(*shape, dtype=F32, scale=1.0, seed=None):
 
 @check
 def gemm_nt():
+    gelu64 = lambda x: 0.5 * x * (1 + torch.erf(x * 0.5 ** 0.5))
+    dgelu64 = lambda x: 0.5 * (1 + torch.erf(x * 0.5 ** 0.5)) + x * torch.exp(-0.5 * x * x) / (2 * math.pi) ** 0.5
     for (M, N, K) in [(162, 192, 64), (5184, 2304, 768), (130, 768, 3072), (64, 48, 192), (512, 512, 48), (4032, 768, 256), (37, 100, 136)]:
+        A, Bm = rnd(M, K, dtype=BF16, seed=1), rnd(N, K, dtype=BF16, scale=0.05, seed=2)
+        prod64 = A.double() @ Bm.double().t()
+        acc64 = kc.C_GEMM * kc.U32 * K * kc.gemm_scale(A, Bm)
         for variant in (0, 1, 2, 3):
             A, Bm = rnd(M, K, dtype=BF16, seed=1), rnd(N, K, dtype=BF16, scale=0.05, seed=2)
             bias, res = rnd(N, seed=3), rnd(M, N, seed=4)
             ref = A.float() @ Bm.float().t() + bias
-            C = torch.empty(M, N, device=dev)
+            pre64 = prod64 + bias.double()
+            tag = f'gemm_nt {M}x{N}x{K} v{variant}'
+            C = kc.poisoned((M, N), F32, dev)
             ops.gemm_nt(A, Bm, M, N, K, bias=bias, C_out=C, variant=variant)
             report(f'gemm_nt {M}x{N}x{K} v{variant} bias', rel(C, ref), 1e-4)
+            elem(tag + ' bias', 'gemm_nt', C, pre64, acc64 + kc.out_round(F32) * pre64.abs())
             # gelu + preact twin, bf16 out
-            U = torch.empty(M, N, device=dev, dtype=BF16)
-            Z = torch.empty(M, N, device=dev, dtype=BF16)
+            U = kc.poisoned((M, N), BF16, dev)
+            Z = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Bm, M, N, K, bias=bias, act=1, C_out=U, c_bf16=True, C2=Z, ldc2=N, c2_mode=1, variant=variant)
             report(f'gemm_nt {M}x{N}x{K} v{variant} gelu', rel(U, torch.nn.functional.gelu(ref)), 6e-3)
             report(f'gemm_nt {M}x{N}x{K} v{variant} preact', rel(Z, ref), 6e-3)
+            elem(tag + ' gelu', 'gemm_nt', U, gelu64(pre64), kc.gelu_bound(acc64, gelu64(pre64), BF16))
+            elem(tag + ' preact', 'gemm_nt', Z, pre64, acc64 + kc.U16 * pre64.abs())
             # gelu fp32 out (the erf approximation itself: |err| <= 1.5e-7) + GELU' twin; then the multiply-only backward form
-            U32 = torch.empty(M, N, device=dev)
-            D = torch.empty(M, N, device=dev, dtype=BF16)
+            U32 = kc.poisoned((M, N), F32, dev)
+            D = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Bm, M, N, K, bias=bias, act=1, C_out=U32, C2=D, ldc2=N, c2_mode=4, variant=variant)
             xg = ref.clone().requires_grad_(True)
             torch.nn.functional.gelu(xg).sum().backward()
             report(f'gemm_nt {M}x{N}x{K} v{variant} gelu32', float((U32 - torch.nn.functional.gelu(ref)).abs().max()), 2e-5)
             report(f"gemm_nt {M}x{N}x{K} v{variant} gelu'twin", float((D.float() - xg.grad).abs().max()), 5e-3)
-            G = torch.empty(M, N, device=dev)
+            elem(tag + ' gelu32', 'gemm_nt', U32, gelu64(pre64), kc.gelu_bound(acc64, gelu64(pre64), F32))
+            elem(tag + " gelu'twin", 'gemm_nt', D, dgelu64(pre64), kc.dgelu_bound(acc64, dgelu64(pre64), BF16))
+            G = kc.poisoned((M, N), F32, dev)
             ops.gemm_nt(A, Bm, M, N, K, act=3, aux=D, ldaux=N, C_out=G, variant=variant)
             report(f'gemm_nt {M}x{N}x{K} v{variant} act3', rel(G, (ref - bias) * D.float()), 1e-4)
-            # residual + beta accumulate + bf16 twin of the final value
-            C = torch.full((M, N), 0.5, device=dev)
-            T = torch.empty(M, N, device=dev, dtype=BF16)
+            g64 = prod64 * D.double()
+            elem(tag + ' act3', 'gemm_nt', G, g64, acc64 * D.double().abs() + kc.out_round(F32) * g64.abs())
+            # residual + beta accumulate (into a random prefill) + bf16 twin of the final value
+            C0 = kc.prefilled((M, N), F32, dev, seed=M + N + variant)
+            C = C0.clone()
+            T = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Bm, M, N, K, res=res, ldres=N, C_out=C, beta=1, C2=T, ldc2=N, c2_mode=3, variant=variant)
-            report(f'gemm_nt {M}x{N}x{K} v{variant} res+beta', rel(C, ref - bias + res + 0.5), 1e-4)
-            report(f'gemm_nt {M}x{N}x{K} v{variant} twin', rel(T, ref - bias + res + 0.5), 6e-3)
+            report(f'gemm_nt {M}x{N}x{K} v{variant} res+beta', rel(C, ref - bias + res + C0), 1e-4)
+            report(f'gemm_nt {M}x{N}x{K} v{variant} twin', rel(T, ref - bias + res + C0), 6e-3)
+            fin64 = prod64 + res.double() + C0.double()
+            elem(tag + ' res+beta', 'gemm_nt', C, fin64, acc64 + kc.out_round(F32) * fin64.abs())
+            elem(tag + ' twin', 'gemm_nt', T, fin64, acc64 + kc.U16 * fin64.abs())
     # every second-generation tile configuration (explicit cfg in variant bits 4-11)
     for (M, N, K) in [(5184, 2304, 768), (300, 200, 128), (4032, 768, 3072)]:
         A, Bm = rnd(M, K, dtype=BF16, seed=1), rnd(N, K, dtype=BF16, scale=0.05, seed=2)
         bias, res = rnd(N, seed=3), rnd(M, N, seed=4)
         ref = A.float() @ Bm.float().t() + bias + res
+        ref64 = A.double() @ Bm.double().t() + bias.double() + res.double()
+        bnd = kc.gemm_bound(A, Bm, ref64, F32)
         experimental = (1, 13, 15, 16, 17, 18, 19, 20, 21, 22) if ops._lib.load().dav_build_flags() & 1 else ()      # make EXPERIMENTAL=1
         for cfg in (3, 5, 7, 8, 60) + experimental:
-            C = torch.empty(M, N, device=dev)
-            ops.gemm_nt(A, Bm, M, N, K, bias=bias, res=res, ldres=N, C_out=C, variant=cfg << 4)
+            g = kc.Guarded(M, N, F32, ld=N + 8 * (cfg % 3), device=dev)            # poisoned, inside guard bands, row stride > N for most
+            C = g.t
+            ops.gemm_nt(A, Bm, M, N, K, bias=bias, res=res, ldres=N, C_out=C, ldc=g.ld, variant=cfg << 4)
             report(f'gemm_nt {M}x{N}x{K} cfg{cfg}', rel(C, ref), 1e-4)
+            elem(f'gemm_nt {M}x{N}x{K} cfg{cfg}', 'gemm_nt', C, ref64, bnd)
+            guard(f'gemm_nt {M}x{N}x{K} cfg{cfg} ldc{g.ld}', g)
     # the big-tile / deep-ring configurations of round 2 (43 / 45 = 256x128, 44 / 46 = 128x256 on 32-deep rings, 7 = 64x64 on
     # four stages) with every epilogue kind the step gives them: staged bf16 output, the SPLIT staged epilogue with a GELU' twin,
     # multiply by aux, fp32 + residual; forward form and b_kn (32-deep stages in b_kn mode are new)
@@ -104,18 +152,32 @@ def gemm_nt():
                 base = A.float() @ (W_kn.float() if bt else W_nk.float().t())
                 var = (cfg << 4) | (bt << 12)
                 tag = f'gemm_nt {M}x{N}x{K} cfg{cfg} b_kn{bt}'
-                U, D = torch.empty(M, N, device=dev, dtype=BF16), torch.empty(M, N, device=dev, dtype=BF16)
-                ops.gemm_nt(A, Wm, M, N, K, bias=bias, act=1, C_out=U, c_bf16=True, C2=D, ldc2=N, c2_mode=4, variant=var, **kw)
+                W64 = W_kn.double().t() if bt else W_nk.double()
+                prod64 = A.double() @ W64.t()
+                acc64 = kc.C_GEMM * kc.U32 * K * (A.double().abs() @ W64.abs().t())
+                pre64 = prod64 + bias.double()
+                gU = kc.Guarded(M, N, BF16, ld=N + 8 * bt, device=dev)
+                U, D = gU.t, kc.poisoned((M, N), BF16, dev)
+                ops.gemm_nt(A, Wm, M, N, K, bias=bias, act=1, C_out=U, ldc=gU.ld, c_bf16=True, C2=D, ldc2=N, c2_mode=4, variant=var, **kw)
                 xg = (base + bias).clone().requires_grad_(True)
                 torch.nn.functional.gelu(xg).sum().backward()
                 report(tag + ' gelu (staged)', rel(U, torch.nn.functional.gelu(base + bias)), 6e-3)
                 report(tag + " gelu' twin (staged)", float((D.float() - xg.grad).abs().max()), 5e-3)
-                G = torch.empty(M, N, device=dev, dtype=BF16)
+                elem(tag + ' gelu (staged)', 'gemm_nt', U, gelu64(pre64), kc.gelu_bound(acc64, gelu64(pre64), BF16))
+                elem(tag + " gelu' twin (staged)", 'gemm_nt', D, dgelu64(pre64), kc.dgelu_bound(acc64, dgelu64(pre64), BF16))
+                guard(tag + ' gelu (staged)', gU)
+                G = kc.poisoned((M, N), BF16, dev)
                 ops.gemm_nt(A, Wm, M, N, K, act=3, aux=aux, ldaux=N, C_out=G, c_bf16=True, variant=var, **kw)
                 report(tag + ' act3 bf16', rel(G, base * aux.float()), 6e-3)
-                C = torch.empty(M, N, device=dev)
-                ops.gemm_nt(A, Wm, M, N, K, bias=bias, res=res, ldres=N, C_out=C, variant=var, **kw)
+                g64 = prod64 * aux.double()
+                elem(tag + ' act3 bf16', 'gemm_nt', G, g64, acc64 * aux.double().abs() + kc.U16 * g64.abs())
+                gC = kc.Guarded(M, N, F32, ld=N + 40 * (1 - bt), device=dev)
+                C = gC.t
+                ops.gemm_nt(A, Wm, M, N, K, bias=bias, res=res, ldres=N, C_out=C, ldc=gC.ld, variant=var, **kw)
                 report(tag + ' fp32 + res', rel(C, base + bias + res), 1e-4)
+                f64 = pre64 + res.double()
+                elem(tag + ' fp32 + res', 'gemm_nt', C, f64, acc64 + kc.out_round(F32) * f64.abs())
+                guard(tag + ' fp32 + res', gC)
     # 256 x 256 tiles (configuration 60, csrc/gemm_nt256.h; K % 128 == 0): every epilogue kind in both operand modes, ragged M / N
     # edges (tiles of 256 on 2100 / 1000 / 300 rows, 200 .. 2304 columns), a K of a single pair of K-tiles, row maps, grouped form
     for (M, N, K) in [(2100, 1024, 512), (1000, 768, 256), (300, 512, 128), (5184, 2304, 768), (517, 200, 384)]:
@@ -127,30 +189,52 @@ def gemm_nt():
             base = A.float() @ (W_kn.float() if bt else W_nk.float().t())
             var = (60 << 4) | (bt << 12)
             tag = f'gemm_nt {M}x{N}x{K} cfg60 b_kn{bt}'
-            U, D = torch.empty(M, N, device=dev, dtype=BF16), torch.empty(M, N, device=dev, dtype=BF16)
+            W64 = W_kn.double().t() if bt else W_nk.double()
+            prod64 = A.double() @ W64.t()
+            acc64 = kc.C_GEMM * kc.U32 * K * (A.double().abs() @ W64.abs().t())
+            pre64 = prod64 + bias.double()
+            U, D = kc.poisoned((M, N), BF16, dev), kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Wm, M, N, K, bias=bias, act=1, C_out=U, c_bf16=True, C2=D, ldc2=N, c2_mode=4, variant=var, **kw)
             xg = (base + bias).clone().requires_grad_(True)
             torch.nn.functional.gelu(xg).sum().backward()
             report(tag + ' gelu', rel(U, torch.nn.functional.gelu(base + bias)), 6e-3)
             report(tag + " gelu' twin", float((D.float() - xg.grad).abs().max()), 5e-3)
-            Z = torch.empty(M, N, device=dev, dtype=BF16)
-            ops.gemm_nt(A, Wm, M, N, K, bias=bias, act=1, C_out=U, c_bf16=True, C2=Z, ldc2=N, c2_mode=1, variant=var, **kw)
+            elem(tag + ' gelu', 'gemm_nt', U, gelu64(pre64), kc.gelu_bound(acc64, gelu64(pre64), BF16))
+            elem(tag + " gelu' twin", 'gemm_nt', D, dgelu64(pre64), kc.dgelu_bound(acc64, dgelu64(pre64), BF16))
+            gZ = kc.Guarded(M, N, BF16, ld=N + 8 * (1 + 4 * bt), device=dev)
+            Z = gZ.t
+            ops.gemm_nt(A, Wm, M, N, K, bias=bias, act=1, C_out=U, c_bf16=True, C2=Z, ldc2=gZ.ld, c2_mode=1, variant=var, **kw)
             report(tag + ' preact twin', rel(Z, base + bias), 6e-3)
-            G = torch.empty(M, N, device=dev, dtype=BF16)
+            elem(tag + ' preact twin', 'gemm_nt', Z, pre64, acc64 + kc.U16 * pre64.abs())
+            guard(tag + f' preact twin ldc2 {gZ.ld}', gZ)
+            G = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Wm, M, N, K, act=3, aux=aux, ldaux=N, C_out=G, c_bf16=True, variant=var, **kw)
             report(tag + ' act3 bf16', rel(G, base * aux.float()), 6e-3)
+            g64 = prod64 * aux.double()
+            elem(tag + ' act3 bf16', 'gemm_nt', G, g64, acc64 * aux.double().abs() + kc.U16 * g64.abs())
             xa = aux.float().requires_grad_(True)
             torch.nn.functional.gelu(xa).sum().backward()
+            G = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Wm, M, N, K, act=2, aux=aux, ldaux=N, C_out=G, c_bf16=True, alpha=0.5, variant=var, **kw)
             report(tag + ' act2 bf16 alpha', rel(G, 0.5 * base * xa.grad), 6e-3)
-            C = torch.full((M, N), 0.25, device=dev)
-            T = torch.empty(M, N, device=dev, dtype=BF16)
+            dg64 = dgelu64(aux.double())
+            a64 = 0.5 * prod64 * dg64
+            elem(tag + ' act2 bf16 alpha', 'gemm_nt', G, a64, 0.5 * acc64 * dg64.abs() + kc.dgelu_bound(0.0, dg64, F32) * 0.5 * prod64.abs() + kc.U16 * a64.abs())
+            C0 = kc.prefilled((M, N), F32, dev, seed=M + bt)
+            C = C0.clone()
+            T = kc.poisoned((M, N), BF16, dev)
             ops.gemm_nt(A, Wm, M, N, K, bias=bias, res=res, ldres=N, C_out=C, beta=1, C2=T, ldc2=N, c2_mode=3, variant=var, **kw)
-            report(tag + ' fp32 + res + beta', rel(C, base + bias + res + 0.25), 1e-4)
-            report(tag + ' final twin', rel(T, base + bias + res + 0.25), 6e-3)
-            P = torch.full((M, N), 7.0, device=dev, dtype=BF16)
-            ops.gemm_nt(A, Wm, M, N, K, C_out=P, c_bf16=True, variant=var, **kw)
+            report(tag + ' fp32 + res + beta', rel(C, base + bias + res + C0), 1e-4)
+            report(tag + ' final twin', rel(T, base + bias + res + C0), 6e-3)
+            f64 = pre64 + res.double() + C0.double()
+            elem(tag + ' fp32 + res + beta', 'gemm_nt', C, f64, acc64 + kc.out_round(F32) * f64.abs())
+            elem(tag + ' final twin', 'gemm_nt', T, f64, acc64 + kc.U16 * f64.abs())
+            gP = kc.Guarded(M, N, BF16, ld=N + 8 * (M % 2), device=dev, fill=7.0)
+            P = gP.t
+            ops.gemm_nt(A, Wm, M, N, K, C_out=P, ldc=gP.ld, c_bf16=True, variant=var, **kw)
             report(tag + ' plain bf16', rel(P, base), 6e-3)
+            elem(tag + ' plain bf16', 'gemm_nt', P, prod64, acc64 + kc.U16 * prod64.abs())
+            guard(tag + f' plain bf16 ldc {gP.ld}', gP)
     # (row maps: A rows 4.. of every batch, C rows 1..)
     Bsz, rpb, tot, N, K = 5, 70, 90, 512, 256
     M = Bsz * rpb
@@ -161,6 +245,16 @@ def gemm_nt():
     ref_full = torch.zeros(Bsz, tot, N, device=dev)
     ref_full[:, 1:1 + rpb] = (Asub.float() @ Bm.float().t()).view(Bsz, rpb, N)
     report('gemm_nt cfg60 rowmaps', rel(Cfull, ref_full.view(-1, N)), 6e-3)
+    # the same launch into poison: mapped rows within their bound, the rows the map skips bit-identical
+    mapped = torch.zeros(Bsz, tot, dtype=torch.bool, device=dev)
+    mapped[:, 1:1 + rpb] = True
+    mapped = mapped.view(-1)
+    Cp = kc.poisoned((Bsz * tot, N), BF16, dev)
+    before = Cp.clone()
+    ops.gemm_nt(Afull, Bm, M, N, K, a_rowmap=(rpb, tot, 4), C_out=Cp, c_bf16=True, c_rowmap=(rpb, tot, 1), variant=60 << 4)
+    ref64 = Asub.double() @ Bm.double().t()
+    elem('gemm_nt cfg60 rowmaps', 'gemm_nt', Cp[mapped], ref64, kc.gemm_bound(Asub, Bm, ref64, BF16))
+    kept('gemm_nt cfg60 rowmaps: rows outside c_rowmap', Cp, before, ~mapped)
     # act 2 (multiply by gelu'(aux)) and row maps
     M, N, K = 3 * 7, 128, 64
     Bsz, rpb, tot = 3, 7, 11
@@ -178,24 +272,48 @@ def gemm_nt():
     ref_full = torch.zeros_like(Cfull).view(Bsz, tot, N)
     ref_full[:, 1:8] = ref.view(Bsz, rpb, N) + resfull.view(Bsz, tot, N)[:, 2:9]
     report('gemm_nt rowmaps+act2', rel(Cfull, ref_full.view(-1, N)), 1e-4)
+    # again into poison: mapped rows elementwise, skipped rows bit-identical
+    mapped = torch.zeros(Bsz, tot, dtype=torch.bool, device=dev)
+    mapped[:, 1:8] = True
+    mapped = mapped.view(-1)
+    Cp = kc.poisoned((Bsz * tot, N), F32, dev)
+    before = Cp.clone()
+    ops.gemm_nt(Afull, Bm, M, N, K, a_rowmap=(rpb, tot, 4), act=2, aux=aux, ldaux=N, res=resfull, ldres=N, res_rowmap=(rpb, tot, 2),
+                C_out=Cp, c_rowmap=(rpb, tot, 1))
+    dg64 = dgelu64(aux.double())
+    p64 = Asub.double() @ Bm.double().t()
+    r64 = p64 * dg64 + resfull.view(Bsz, tot, N)[:, 2:9].reshape(M, N).double()
+    elem('gemm_nt rowmaps+act2', 'gemm_nt', Cp[mapped], r64,
+         kc.C_GEMM * kc.U32 * K * kc.gemm_scale(Asub, Bm) * dg64.abs() + kc.dgelu_bound(0.0, dg64, F32) * p64.abs() + kc.out_round(F32) * r64.abs())
+    kept('gemm_nt rowmaps+act2: rows outside c_rowmap', Cp, before, ~mapped)
     rows = torch.randint(0, 5, (M,), device=dev, dtype=torch.int32)
     pos = rnd(5, N, seed=9)
-    C = torch.empty(M, N, device=dev)
+    C = kc.poisoned((M, N), F32, dev)
     ops.gemm_nt(Asub.contiguous(), Bm, M, N, K, res=pos, ldres=N, res_rows=rows, C_out=C)
     report('gemm_nt res_rows', rel(C, Asub.float() @ Bm.float().t() + pos[rows.long()]), 1e-4)
+    r64 = Asub.double() @ Bm.double().t() + pos.double()[rows.long()]
+    elem('gemm_nt res_rows', 'gemm_nt', C, r64, kc.gemm_bound(Asub, Bm, r64, F32))
     # B given as [K, N] (dgrad reading W itself), incl. column offset / ldb and all tile configs
     for (M2, N2, K2) in [(300, 768, 192), (5184, 768, 2304), (2048, 136, 64), (4032, 3072, 768)]:
         A2 = rnd(M2, K2, dtype=BF16, seed=15)
         Wkn = rnd(K2, 2 * N2, dtype=BF16, scale=0.05, seed=16)
+        W64 = Wkn[:, N2:].t()
+        r64 = A2.double() @ W64.double().t()
+        bnd = kc.gemm_bound(A2, W64, r64, F32)
         for cfg in (0, 3, 8, 5):
-            C = torch.empty(M2, N2, device=dev)
-            ops.gemm_nt(A2, Wkn.view(-1)[N2:], M2, N2, K2, ldb=2 * N2, C_out=C, variant=(1 << 12) | (cfg << 4))
+            g = kc.Guarded(M2, N2, F32, ld=N2 + 8 * (cfg % 2), device=dev)
+            C = g.t
+            ops.gemm_nt(A2, Wkn.view(-1)[N2:], M2, N2, K2, ldb=2 * N2, C_out=C, ldc=g.ld, variant=(1 << 12) | (cfg << 4))
             report(f'gemm_nt b_kn {M2}x{N2}x{K2} cfg{cfg}', rel(C, A2.float() @ Wkn[:, N2:].float()), 1e-4)
+            elem(f'gemm_nt b_kn {M2}x{N2}x{K2} cfg{cfg}', 'gemm_nt', C, r64, bnd)
+            guard(f'gemm_nt b_kn {M2}x{N2}x{K2} cfg{cfg} ldc {g.ld}', g)
     # B sub-matrix (column offset, ldb)
     Bw = rnd(N, 2 * K, dtype=BF16, scale=0.1, seed=10)
-    C = torch.empty(M, N, device=dev)
+    C = kc.poisoned((M, N), F32, dev)
     ops.gemm_nt(Asub.contiguous(), Bw.view(-1)[K:], M, N, K, ldb=2 * K, C_out=C)
     report('gemm_nt ldb/offset', rel(C, Asub.float() @ Bw[:, K:].float().t()), 1e-4)
+    r64 = Asub.double() @ Bw[:, K:].double().t()
+    elem('gemm_nt ldb/offset', 'gemm_nt', C, r64, kc.gemm_bound(Asub, Bw[:, K:], r64, F32))
 
 
 @check
@@ -204,44 +322,76 @@ def gemm_tn():
         for variant in (0, 1, 2, 16, 32):
             A, Bm = rnd(Mc, N, dtype=BF16, seed=11), rnd(Mc, K, dtype=BF16, seed=12)
             ref = A.float().t() @ Bm.float()
-            C = torch.zeros(N, K, device=dev)
-            bg = torch.zeros(N, device=dev)
+            P0, pb0 = kc.prefilled((N, K), F32, dev, seed=Mc + variant), kc.prefilled((N,), F32, dev, seed=N + variant)
+            C = P0.clone()
+            bg = pb0.clone()
             ops.gemm_tn(A, Bm, Mc, N, K, C, beta=1, bias_grad=bg, variant=variant)
-            report(f'gemm_tn {Mc}x{N}x{K} v{variant} acc', rel(C, ref), 2e-4)
-            report(f'gemm_tn {Mc}x{N}x{K} v{variant} bias_grad', rel(bg, A.float().sum(0)), 2e-4)
-            C = torch.full((N, K), 7.0, device=dev)
-            ops.gemm_tn(A, Bm, Mc, N, K, C, beta=0, variant=variant)
+            report(f'gemm_tn {Mc}x{N}x{K} v{variant} acc', rel(C, P0 + ref), 2e-4)
+            report(f'gemm_tn {Mc}x{N}x{K} v{variant} bias_grad', rel(bg, pb0 + A.float().sum(0)), 2e-4)
+            r64 = A.double().t() @ Bm.double()
+            bnd = kc.gemm_bound(A.t(), Bm.t(), r64, F32)
+            elem(f'gemm_tn {Mc}x{N}x{K} v{variant} acc', 'gemm_tn', C, P0.double() + r64, bnd + kc.out_round(F32) * P0.double().abs())
+            b64 = pb0.double() + A.double().sum(0)
+            elem(f'gemm_tn {Mc}x{N}x{K} v{variant} bias_grad', 'gemm_tn', bg, b64, kc.C_GEMM * kc.U32 * Mc * A.double().abs().sum(0) + kc.out_round(F32) * b64.abs())
+            gS = kc.Guarded(N, K, F32, ld=K + 8 * (variant % 3), device=dev, fill=7.0)
+            C = gS.t
+            ops.gemm_tn(A, Bm, Mc, N, K, C, ldc=gS.ld, beta=0, variant=variant)
             report(f'gemm_tn {Mc}x{N}x{K} v{variant} store', rel(C, ref), 2e-4)
-    # grouped launch of several problems (deferred wgrads of a layer), incl. bias grads and the split-K path
-    probs, refs = [], []
+            elem(f'gemm_tn {Mc}x{N}x{K} v{variant} store', 'gemm_tn', C, r64, bnd)
+            guard(f'gemm_tn {Mc}x{N}x{K} v{variant} store ldc {gS.ld}', gS)
+    # grouped launch of several problems (deferred wgrads of a layer), incl. bias grads and the split-K path; every gradient starts
+    # from a random prefill inside its own guard bands (a stray write into a neighbour's gradient shows there)
+    probs, refs, pres = [], [], []
     for i, (Mc, N, K) in enumerate([(3136, 768, 768), (3136, 2304, 768), (4032, 768, 3072), (512, 192, 768), (2048, 72, 136), (6080, 3072, 768)]):
         A, Bm = rnd(Mc, N, dtype=BF16, seed=60 + i), rnd(Mc, K, dtype=BF16, seed=70 + i)
-        C = torch.full((N, K), 0.25, device=dev)
-        bg = torch.full((N,), 0.5, device=dev) if i % 2 == 0 else None
-        probs.append(dict(A=A, B=Bm, Mc=Mc, N=N, K=K, C=C, lda=N, ldb=K, ldc=K, bias_grad=bg))
-        refs.append((C, 0.25 + A.float().t() @ Bm.float(), bg, None if bg is None else 0.5 + A.float().sum(0)))
+        P0, pb0 = kc.prefilled((N, K), F32, dev, seed=80 + i), kc.prefilled((N,), F32, dev, seed=90 + i)
+        gC = kc.Guarded(N, K, F32, ld=K + 8 * (i % 3), device=dev, fill=P0)
+        C = gC.t
+        bg = pb0.clone() if i % 2 == 0 else None
+        probs.append(dict(A=A, B=Bm, Mc=Mc, N=N, K=K, C=C, lda=N, ldb=K, ldc=gC.ld, bias_grad=bg, guard=gC))
+        refs.append((C, P0 + A.float().t() @ Bm.float(), bg, None if bg is None else pb0 + A.float().sum(0)))
+        pres.append((P0, pb0))
+
+    def tn_elem(tag, i, times=1, written=False):
+        """gradient == (0 if written else prefill) + times * A^T B, bias == prefill + times * colsum(A), each element within its bound"""
+        pr, (P0, pb0) = probs[i], pres[i]
+        r64 = (0.0 if written else P0.double()) + times * (pr['A'].double().t() @ pr['B'].double())
+        elem(tag + ' C', 'gemm_tn', pr['C'], r64, times * kc.gemm_bound(pr['A'].t(), pr['B'].t(), r64, F32))
+        if pr['bias_grad'] is not None:
+            b64 = pb0.double() + times * pr['A'].double().sum(0)
+            elem(tag + ' bias', 'gemm_tn', pr['bias_grad'], b64,
+                 times * kc.C_GEMM * kc.U32 * pr['Mc'] * pr['A'].double().abs().sum(0) + kc.out_round(F32) * b64.abs())
+        guard(tag + f' ldc {pr["ldc"]}', pr['guard'])
     ops.gemm_tn_grouped(probs)
     for i, (C, rc, bg, rb) in enumerate(refs):
         report(f'gemm_tn grouped #{i} C', rel(C, rc), 2e-4)
         if bg is not None:
             report(f'gemm_tn grouped #{i} bias', rel(bg, rb), 2e-4)
+        tn_elem(f'gemm_tn grouped #{i}', i)
     ops.gemm_tn_grouped(probs[:2])        # small group -> split-K atomics path
-    report('gemm_tn grouped split acc', rel(refs[0][0], 2 * refs[0][1] - 0.25), 2e-4)
+    report('gemm_tn grouped split acc', rel(refs[0][0], 2 * refs[0][1] - pres[0][0]), 2e-4)
+    for i in range(2):
+        tn_elem(f'gemm_tn grouped split #{i}', i, times=2)
     # written (not accumulated) tiles: DavTnProblem.flags bit 0 — old contents (NaN here) are ignored, the bias gradient still
     # accumulates, never split over the contraction (a small group would otherwise take the atomics path); mixed with an accumulating problem
     for group in (probs[:2], probs):
         for i, pr in enumerate(group):
             pr['overwrite'] = i != 1
-            pr['C'].fill_(float('nan') if pr['overwrite'] else 0.25)
+            if pr['overwrite']:
+                pr['C'].fill_(float('nan'))
+            else:
+                pr['C'].copy_(pres[i][0])
             if pr['bias_grad'] is not None:
-                pr['bias_grad'].fill_(0.5)
+                pr['bias_grad'].copy_(pres[i][1])
         ops.gemm_tn_grouped(group)
         for i, (C, rc, bg, rb) in enumerate(refs[:len(group)]):
-            report(f'gemm_tn grouped[{len(group)}] #{i} {"written" if i != 1 else "accumulated"}', rel(C, rc - (0.25 if i != 1 else 0.0)), 2e-4)
+            report(f'gemm_tn grouped[{len(group)}] #{i} {"written" if i != 1 else "accumulated"}', rel(C, rc - (pres[i][0] if i != 1 else 0.0)), 2e-4)
             if bg is not None:
                 report(f'gemm_tn grouped[{len(group)}] #{i} bias', rel(bg, rb), 2e-4)
+            tn_elem(f'gemm_tn grouped[{len(group)}] #{i} {"written" if i != 1 else "accumulated"}', i, written=i != 1)
     for pr in probs:
         pr.pop('overwrite')
+        pr.pop('guard')
     # row maps + ldc sub-block
     Bsz, rpb, tot, N, K = 3, 5, 9, 64, 128
     Af, Bf = rnd(Bsz * tot, N, dtype=BF16, seed=13), rnd(Bsz * tot, K, dtype=BF16, seed=14)
@@ -252,6 +402,12 @@ def gemm_tn():
     ref = torch.zeros_like(Cw)
     ref[:, K:] = As.float().t() @ Bs.float()
     report('gemm_tn rowmaps+ldc', rel(Cw, ref), 2e-4)
+    gW = kc.Guarded(N, K, F32, ld=2 * K, device=dev, fill=kc.prefilled((N, K), F32, dev, seed=99))
+    P0 = gW.t.clone()
+    ops.gemm_tn(Af, Bf, Bsz * rpb, N, K, gW.t, ldc=gW.ld, a_rowmap=(rpb, tot, 2), b_rowmap=(rpb, tot, 4), beta=1)
+    r64 = P0.double() + As.double().t() @ Bs.double()
+    elem('gemm_tn rowmaps+ldc (prefilled)', 'gemm_tn', gW.t, r64, kc.gemm_bound(As.t(), Bs.t(), r64, F32))
+    guard('gemm_tn rowmaps+ldc (prefilled) ldc 2K', gW)
 
 
 @check
@@ -262,26 +418,32 @@ def gemm_tn_gang():
               (64, 256, 256), (192, 1032, 40), (5184, 2304, 768), (6080, 3072, 1024),
               (2592, 1024, 1024), (3040, 1024, 3072), (1568, 4096, 1024), (40, 264, 520), (200, 8, 8), (63 * 8, 768, 192)]      # ragged: Mc % 64 != 0
     for mode in ('accumulate', 'written', 'mixed'):
-        probs, refs = [], []
+        probs, refs, guards = [], [], []
         for i, (Mc, N, K) in enumerate(shapes):
             A, Bm = rnd(Mc, N, dtype=BF16, seed=160 + i), rnd(Mc, K, dtype=BF16, seed=170 + i)
             ow = mode == 'written' or (mode == 'mixed' and i % 2 == 0)
-            C = torch.full((N, K), float('nan') if ow else 0.25, device=dev)
+            gC = kc.Guarded(N, K, F32, ld=K + 8 * (0, 0, 1, 5)[i % 4], device=dev, fill=float('nan') if ow else 0.25)
+            C = gC.t
             bg = torch.full((N,), 0.5, device=dev) if i % 3 != 1 else None
-            probs.append(dict(A=A, B=Bm, Mc=Mc, N=N, K=K, C=C, lda=N, ldb=K, ldc=K, bias_grad=bg, overwrite=ow))
+            probs.append(dict(A=A, B=Bm, Mc=Mc, N=N, K=K, C=C, lda=N, ldb=K, ldc=gC.ld, bias_grad=bg, overwrite=ow))
             refs.append((C, (0.0 if ow else 0.25) + A.float().t() @ Bm.float(), bg, None if bg is None else 0.5 + A.float().sum(0)))
-        ops.gemm_tn_gang(probs)
+            guards.append(gC)
+        kc.gang(probs)
         for i, (C, rc, bg, rb) in enumerate(refs):
             report(f'gemm_tn_gang {mode} #{i} {shapes[i]} C', rel(C, rc), 2e-4)
             if bg is not None:
                 report(f'gemm_tn_gang {mode} #{i} bias', rel(bg, rb), 2e-4)
+            pr = probs[i]
+            r64 = (0.0 if pr['overwrite'] else 0.25) + pr['A'].double().t() @ pr['B'].double()
+            elem(f'gemm_tn_gang {mode} #{i} {shapes[i]} C', 'gemm_tn_gang', C, r64, kc.gemm_bound(pr['A'].t(), pr['B'].t(), r64, F32))
+            guard(f'gemm_tn_gang {mode} #{i} {shapes[i]} ldc {pr["ldc"]}', guards[i])
     # bit-repeatable whoever draws which ticket: the same launch twice, written tiles
     Cs = []
     for _ in range(2):
         for pr in probs:
             pr['overwrite'] = True
-            pr['C'] = torch.empty_like(pr['C'])
-        ops.gemm_tn_gang(probs)
+            pr['C'], pr['ldc'] = kc.poisoned((pr['N'], pr['K']), F32, dev), pr['K']
+        kc.gang(probs)
         torch.cuda.synchronize()
         Cs.append([pr['C'].clone() for pr in probs])
     report('gemm_tn_gang bit-repeatable', float(max((a != b).sum() for a, b in zip(*Cs))), 0.0)
@@ -297,6 +459,13 @@ def gemm_tn_gang():
         ref = torch.zeros_like(Cw)
         ref[:, K:] = As.float().t() @ Bs.float()
         report(f'gemm_tn_gang rowmaps+ldc rpb={rpb}', rel(Cw, ref), 2e-4)
+        # written into poison with a row stride of K + 24, inside guards (0xFF workspace)
+        gC = kc.Guarded(N, K, F32, ld=K + 24, device=dev)
+        kc.gang([dict(A=Af, B=Bf, Mc=Mc, N=N, K=K, C=gC.t, lda=N, ldb=K, ldc=gC.ld, a_rowmap=(rpb, tot, offa), b_rowmap=(rpb, tot, offb),
+                   bias_grad=None, overwrite=True)])
+        r64 = As.double().t() @ Bs.double()
+        elem(f'gemm_tn_gang rowmaps written rpb={rpb}', 'gemm_tn_gang', gC.t, r64, kc.gemm_bound(As.t(), Bs.t(), r64, F32))
+        guard(f'gemm_tn_gang rowmaps written rpb={rpb} ldc {gC.ld}', gC)
     # a few hundred problems in one launch (several table-writer launches)
     many, refs = [], []
     for i in range(150):
@@ -310,7 +479,7 @@ def gemm_tn_gang():
     # one very wide weight: 50 x 50 tiles = 104 gangs, more than one table-writer launch carries (its tickets span two), beside a small one
     A, Bm = rnd(64, 12800, dtype=BF16, seed=700), rnd(64, 12800, dtype=BF16, seed=701)
     A2, B2 = rnd(100, 264, dtype=BF16, seed=702), rnd(100, 40, dtype=BF16, seed=703)
-    Cbig, C2 = torch.empty(12800, 12800, device=dev), torch.zeros(264, 40, device=dev)
+    Cbig, C2 = kc.poisoned((12800, 12800), F32, dev), torch.zeros(264, 40, device=dev)
     ops.gemm_tn_gang([dict(A=A, B=Bm, Mc=64, N=12800, K=12800, C=Cbig, lda=12800, ldb=12800, ldc=12800, bias_grad=None, overwrite=True),
                       dict(A=A2, B=B2, Mc=100, N=264, K=40, C=C2, lda=264, ldb=40, ldc=40, bias_grad=None)])
     report('gemm_tn_gang 12800 x 12800 weight (104 gangs)', rel(Cbig, A.float().t() @ Bm.float()), 2e-4)
@@ -330,12 +499,12 @@ def patch_gather3d():
         gt, gh, gw = T // pt, H // 16, W // 16
         L = gt * gh * gw
         cols = x.view(B, C, gt, pt, gh, 16, gw, 16).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, L, C * pt * 256)
-        A = torch.empty(B * L, C * pt * 256, device=dev, dtype=BF16)
+        A = kc.poisoned((B * L, C * pt * 256), BF16, dev)
         ops.patch_gather(x, None, L, A, pt)
         report(f'patch_gather3d all {B}x{C}x{T}x{H}x{W}', rel(A.view(B, L, -1), cols.to(BF16)), 1e-6)
         nk = max(1, L // 3)
         ids = torch.stack([torch.randperm(L, device=dev)[:nk] for _ in range(B)]).to(torch.int32)
-        A2 = torch.empty(B * nk, C * pt * 256, device=dev, dtype=BF16)
+        A2 = kc.poisoned((B * nk, C * pt * 256), BF16, dev)
         ops.patch_gather(x, ids, nk, A2, pt)
         ref = torch.gather(cols, 1, ids.long().unsqueeze(-1).expand(-1, -1, cols.shape[-1]))
         report(f'patch_gather3d kept {B}x{C}x{T}x{H}x{W}', rel(A2.view(B, nk, -1), ref.to(BF16)), 1e-6)
@@ -371,8 +540,8 @@ def attention():
             q, k, v = qb.permute(0, 2, 1, 3).float(), kb.permute(0, 2, 1, 3).float(), vb.permute(0, 2, 1, 3).float()
         q.requires_grad_(True); k.requires_grad_(True); v.requires_grad_(True)
         ref = ref_attn(q, k, v, scale)
-        O = torch.empty(B * Nq, H * dv, device=dev, dtype=BF16)
-        LSE = torch.empty(B, H, Nq, device=dev)
+        O = kc.poisoned((B * Nq, H * dv), BF16, dev)
+        LSE = kc.poisoned((B, H, Nq), F32, dev)
         p = lambda t: t[0].data_ptr() + 2 * t[1]
         ops.attn_fwd(p(qt), p(kt), p(vt), O, LSE, B, H, Nq, Nk, dqk, dv, *strides, Nq * H * dv, H * dv, scale)
         tag = f'attn B{B} H{H} {Nq}x{Nk} d{dqk}/{dv}'
@@ -381,11 +550,15 @@ def attention():
         report(tag + ' lse', rel(LSE, lse_ref), 1e-4)
         dO = rnd(B * Nq, H * dv, dtype=BF16, seed=25)
         ref.backward(dO.view(B, Nq, H, dv).permute(0, 2, 1, 3).float())
+        Ok = O.view(B, Nq, H, dv).permute(0, 2, 1, 3)
+        r64 = kc.attn_bounds(q, k, v, dO.view(B, Nq, H, dv).permute(0, 2, 1, 3), Ok, scale)
+        elem(tag + ' fwd', 'attention', Ok, r64['O'], r64['bO'])
+        elem(tag + ' lse', 'attention', LSE, r64['lse'], r64['blse'])
         if fused:
-            dbuf = torch.zeros_like(buf)
+            dbuf = kc.poisoned(buf.shape, BF16, dev)                 # the q slots of the qo context rows stay poisoned (checked below)
             dqt = (dbuf, qt[1]); dkt = (dbuf, kt[1]); dvt = (dbuf, vt[1])
         else:
-            dqb, dkb, dvb = torch.zeros_like(qb), torch.zeros_like(kb), torch.zeros_like(vb)
+            dqb, dkb, dvb = (kc.poisoned(t.shape, BF16, dev) for t in (qb, kb, vb))
             dqt, dkt, dvt = (dqb, 0), (dkb, 0), (dvb, 0)
         Delta = torch.empty_like(LSE)
         ops.attn_bwd(p(qt), p(kt), p(vt), O, dO, LSE, Delta, p(dqt), p(dkt), p(dvt), B, H, Nq, Nk, dqk, dv, *strides,
@@ -397,14 +570,22 @@ def attention():
         report(tag + ' dq', rel(gq, q.grad), 2e-2)
         report(tag + ' dk', rel(gk, k.grad), 2e-2)
         report(tag + ' dv', rel(gv, v.grad), 2e-2)
+        elem(tag + ' dq', 'attention', gq, r64['dq'], r64['bdq'])
+        elem(tag + ' dk', 'attention', gk, r64['dk'], r64['bdk'])
+        elem(tag + ' dv', 'attention', gv, r64['dv'], r64['bdv'])
         if fused and qo > 0:
             # dav_attn_bwd_ctx: the dQ kernel zero-fills the q slots of the qo context-only rows in front of the queries — into a
             # buffer full of NaNs the whole fused gradient must come out equal to the one written into zeros above
+            ctx = torch.zeros(B, Nk, 3, dtype=torch.bool, device=dev)
+            ctx[:, :qo, 0] = True
+            kept(tag + f' q slots of the {qo} context rows (plain backward)', dbuf, kc.poisoned(buf.shape, BF16, dev), ctx)
             dbuf2 = torch.full_like(buf, float('nan'))
             ops.attn_bwd(p(qt), p(kt), p(vt), O, dO, LSE, Delta, dbuf2.data_ptr() + 2 * qt[1], dbuf2.data_ptr() + 2 * kt[1],
                          dbuf2.data_ptr() + 2 * vt[1], B, H, Nq, Nk, dqk, dv, *strides, Nq * H * dv, H * dv, Nq * H * dv, H * dv,
                          *strides, scale, dq_ctx_rows=qo)
-            same = torch.equal(dbuf2, dbuf) and float(dbuf2[:, :qo, 0].abs().max()) == 0.0
+            want = dbuf.clone()
+            want[:, :qo, 0] = 0.0
+            same = torch.equal(dbuf2, want) and float(dbuf2[:, :qo, 0].abs().max()) == 0.0
             report(tag + f' ctx rows {qo}', 0.0 if same else 1.0, 1e-9)
 
 
@@ -445,8 +626,8 @@ def dropout():
                 q, k, v = qb.permute(0, 2, 1, 3).float(), kb.permute(0, 2, 1, 3).float(), vb.permute(0, 2, 1, 3).float()
             q.requires_grad_(True); k.requires_grad_(True); v.requires_grad_(True)
             ref = (((q @ k.transpose(-2, -1)) * scale).softmax(-1) * km) @ v
-            O = torch.empty(B * Nq, H * dv, device=dev, dtype=dt)
-            LSE = torch.empty(B, H, Nq, device=dev)
+            O = kc.poisoned((B * Nq, H * dv), dt, dev)
+            LSE = kc.poisoned((B, H, Nq), F32, dev)
             p = lambda t: t[0].data_ptr() + es * t[1]
             ops.attn_drop_fwd(p(qt), p(kt), p(vt), O, LSE, B, H, Nq, Nk, dqk, dv, *strides, Nq * H * dv, H * dv, scale, keep, ld, 1.0 / keep_p)
             tag = f'attn_drop {"f32" if f32 else "bf16"} B{B} H{H} {Nq}x{Nk} d{dqk}/{dv} p{pdrop}'
@@ -455,12 +636,17 @@ def dropout():
             report(tag + ' lse', rel(LSE, torch.logsumexp((q @ k.transpose(-2, -1)) * scale, -1)), 1e-4)
             dO = rnd(B * Nq, H * dv, dtype=dt, seed=25)
             ref.backward(dO.view(B, Nq, H, dv).permute(0, 2, 1, 3).float())
-            fill = float('nan') if (fused and qo > 0 and not f32) else 0.0       # bf16: the dQ kernel zero-fills the context rows' q slots
+            Ok = O.view(B, Nq, H, dv).permute(0, 2, 1, 3)
+            up, ro = (2.0 ** -18, 4 * kc.U32) if f32 else (kc.U16, kc.U16)
+            r64 = kc.attn_bounds(q, k, v, dO.view(B, Nq, H, dv).permute(0, 2, 1, 3), Ok, scale, keep=km, up=up, r_out=ro)
+            elem(tag + ' fwd', 'dropout', Ok, r64['O'], r64['bO'])
+            elem(tag + ' lse', 'dropout', LSE, r64['lse'], r64['blse'])
+            fill = float('nan')             # written outputs (bf16 with context rows: the dQ kernel zero-fills their q slots)
             if fused:
                 dbuf = torch.full_like(buf, fill)
                 dqt = (dbuf, qt[1]); dkt = (dbuf, kt[1]); dvt = (dbuf, vt[1])
             else:
-                dqb, dkb, dvb = torch.zeros_like(qb), torch.zeros_like(kb), torch.zeros_like(vb)
+                dqb, dkb, dvb = (kc.poisoned(t.shape, dt, dev) for t in (qb, kb, vb))
                 dqt, dkt, dvt = (dqb, 0), (dkb, 0), (dvb, 0)
             Delta = torch.empty_like(LSE)
             ops.attn_drop_bwd(p(qt), p(kt), p(vt), O, dO, LSE, Delta, p(dqt), p(dkt), p(dvt), B, H, Nq, Nk, dqk, dv, *strides,
@@ -468,13 +654,20 @@ def dropout():
                               dq_ctx_rows=qo if not f32 else 0)
             if fused:
                 gq = dbuf[:, qo:qo + Nq, 0].permute(0, 2, 1, 3); gk = dbuf[:, :, 1].permute(0, 2, 1, 3); gv = dbuf[:, :, 2].permute(0, 2, 1, 3)
-                if fill != 0.0:
+                if qo > 0 and not f32:
                     report(tag + f' ctx rows {qo}', float(dbuf[:, :qo, 0].abs().max().nan_to_num(nan=1.0)), 1e-9)
+                elif qo > 0:
+                    ctx = torch.zeros(B, Nk, 3, dtype=torch.bool, device=dev)
+                    ctx[:, :qo, 0] = True
+                    kept(tag + f' q slots of the {qo} context rows', dbuf, torch.full_like(buf, fill), ctx)
             else:
                 gq, gk, gv = dqb.permute(0, 2, 1, 3), dkb.permute(0, 2, 1, 3), dvb.permute(0, 2, 1, 3)
             report(tag + ' dq', rel(gq, q.grad), tb)
             report(tag + ' dk', rel(gk, k.grad), tb)
             report(tag + ' dv', rel(gv, v.grad), tb)
+            elem(tag + ' dq', 'dropout', gq, r64['dq'], r64['bdq'])
+            elem(tag + ' dk', 'dropout', gk, r64['dk'], r64['bdk'])
+            elem(tag + ' dv', 'dropout', gv, r64['dv'], r64['bdv'])
     # dropout on activations, DropPath folded in
     for (B, rows, D) in [(4, 49, 768), (3, 7, 128), (2, 204, 3072), (1, 1, 4)]:
         g = torch.Generator(device='cpu'); g.manual_seed(7 + rows)
@@ -492,8 +685,16 @@ def dropout():
                         ref = (ref.view(B, rows, D) * rsc.view(B, 1, 1)).reshape(B * rows, D)
                     if rr is not None:
                         ref = ref + rr
-                    out = torch.empty(B * rows, D, device=dev, dtype=dout)
+                    out = kc.poisoned((B * rows, D), dout, dev)
                     ops.dropout_rows(x, kp, 1.0 / 0.8, B, rows, D, out, res=rr, rowscale=rsc)
+                    r64 = x.double() * (1.0 if kp is None else kp.double() * float(torch.tensor(1.0 / 0.8)))
+                    if rsc is not None:
+                        r64 = (r64.view(B, rows, D) * rsc.double().view(B, 1, 1)).reshape(B * rows, D)
+                    mag = r64.abs() + (0.0 if rr is None else rr.double().abs())
+                    if rr is not None:
+                        r64 = r64 + rr.double()
+                    elem(f'dropout_rows {B}x{rows}x{D} {str(din)[6:]}->{str(dout)[6:]} keep{kp is not None} rs{rsc is not None} res{rr is not None}',
+                         'dropout', out, r64, 4 * kc.U32 * mag + (kc.U16 * r64.abs() if dout == BF16 else 0.0))
                     report(f'dropout_rows {B}x{rows}x{D} {str(din)[6:]}->{str(dout)[6:]} keep{kp is not None} rs{rsc is not None} res{rr is not None}',
                            rel(out, ref.to(dout)), 1e-6 if dout == F32 else 4e-3)
                 if din == dout:         # in place
@@ -524,7 +725,7 @@ def window_attention():
             mask = torch.where(rnd(nW, A, A, seed=72) > 0.3, torch.full((nW, A, A), -100.0, device=dev), torch.zeros(nW, A, A, device=dev))
             mask[:, torch.arange(A), torch.arange(A)] = 0.0            # a row never masks itself
         nb = nW if masked else 1
-        bias2 = torch.empty(nb, H, N, ld, device=dev)
+        bias2 = kc.poisoned((nb, H, N, ld), F32, dev)
         ops.relpos_bias_build(table, index32, mask, nb, H, A, N, ld, LOG2E, bias2)
         full = torch.zeros(nb, H, N, N, device=dev)
         full[:, :, :A, :A] = table[index.reshape(-1)].view(A, A, H).permute(2, 0, 1)[None] + (mask[:, None] if masked else 0.0)
@@ -537,8 +738,8 @@ def window_attention():
         logits = (q @ k.transpose(-2, -1)) * scale + full.repeat(B * nW // nb, 1, 1, 1)
         logits.retain_grad()
         ref = logits.softmax(-1) @ v
-        O = torch.empty(B * nW * N, D, device=dev, dtype=BF16)
-        LSE = torch.empty(B * nW, H, N, device=dev)
+        O = kc.poisoned((B * nW * N, D), BF16, dev)
+        LSE = kc.poisoned((B * nW, H, N), F32, dev)
         st = (N * 3 * D, 3 * D) * 3
         p0 = buf.data_ptr()
         ops.attn_bias_fwd(p0, p0 + 2 * D, p0 + 4 * D, O, LSE, B * nW, H, N, N, d, d, *st, N * D, D, scale, bias2, nb, ld)
@@ -566,13 +767,13 @@ def window_attention():
         rows = torch.randperm(L, generator=torch.Generator().manual_seed(5)).to(dev)
         inv = torch.empty_like(rows); inv[rows] = torch.arange(L, device=dev)
         x = rnd(B, nF + L, C, seed=75)
-        seq = torch.empty(B * nW * N, C, device=dev, dtype=BF16)
+        seq = kc.poisoned((B * nW * N, C), BF16, dev)
         ops.window_unfold(x, rows.to(torch.int32), B, nW, A, nF, L, C, 0.5, seq)
         want = torch.cat([x[:, nF:][:, rows].reshape(B * nW, A, C), (0.5 * x[:, None, :nF]).expand(B, nW, nF, C).reshape(B * nW, nF, C)], 1)
         report(f'window_unfold nW{nW} nF{nF}', rel(seq.view(B * nW, N, C), want), 4e-3)
         t = rnd(B * nW * N, C, seed=76)
         res = rnd(B, nF + L, C, seed=77)
-        out = torch.empty(B, nF + L, C, device=dev)
+        out = kc.poisoned((B, nF + L, C), F32, dev)
         ops.window_fold(t, inv.to(torch.int32), res, B, nW, A, nF, L, C, 1.0 / nW, out)
         tv = t.view(B, nW, N, C)
         tok = torch.empty(B, L, C, device=dev)
@@ -592,8 +793,8 @@ def layernorm():
         gp, bp = g.clone().requires_grad_(True), bt.clone().requires_grad_(True)
         ref = torch.nn.functional.layer_norm(xc, (D,), gp, bp, 1e-6)
         R = r0 + r1
-        y, y32 = torch.empty(B * R, D, device=dev, dtype=BF16), torch.empty(B * R, D, device=dev)
-        mean, rstd = torch.empty(B * R, device=dev), torch.empty(B * R, device=dev)
+        y, y32 = kc.poisoned((B * R, D), BF16, dev), kc.poisoned((B * R, D), F32, dev)
+        mean, rstd = kc.poisoned((B * R,), F32, dev), kc.poisoned((B * R,), F32, dev)
         a0, a1 = (x0, x1) if x0 is not None else (x1, None)
         n0, n1 = (r0, r1) if x0 is not None else (r1, 0)
         ops.layernorm_fwd(a0, n0 * D, n0, a1, n1 * D, n1, B, D, g, bt, 1e-6, y, y32, mean, rstd)
@@ -603,19 +804,44 @@ def layernorm():
         dy = rnd(B * R, D, dtype=BF16, seed=35)
         dy32 = rnd(B * R, D, seed=36)
         ref.backward((dy.float() + dy32).view(B, R, D))
-        dx0 = torch.full((B, n0, D), 1.0, device=dev)
+        L = kc.ln_bounds(xc.view(-1, D), g, bt, 1e-6, dy.double() + dy32.double())
+        elem(tag + ' fwd32', 'layernorm', y32, L['y'], L['by'] + kc.out_round(F32) * L['y'].abs())
+        elem(tag + ' fwd16', 'layernorm', y, L['y'], L['by'] + kc.U16 * L['y'].abs())
+        elem(tag + ' mean', 'layernorm', mean, L['mean'], kc.C_LN * kc.U32 * xc.view(-1, D).double().abs().mean(-1))
+        elem(tag + ' rstd', 'layernorm', rstd, L['rstd'], kc.C_LN * kc.U32 * L['rstd'])
+        P0 = kc.prefilled((B, n0, D), F32, dev, seed=38)
+        dx0 = P0.clone()
         res0 = rnd(B, n0, D, seed=37)
-        tw0 = torch.empty(B, n0, D, device=dev, dtype=BF16)
-        dx1 = torch.empty(B, max(n1, 1), D, device=dev)[:, :n1].contiguous() if n1 else None
-        dg, db = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
+        tw0 = kc.poisoned((B, n0, D), BF16, dev)
+        dx1 = kc.poisoned((B, n1, D), F32, dev) if n1 else None
+        pg, pb = kc.prefilled((D,), F32, dev, seed=39), kc.prefilled((D,), F32, dev, seed=40)
+        dg, db = pg.clone(), pb.clone()
         ops.layernorm_bwd(a0, n0 * D, n0, a1, n1 * D, n1, B, D, dy, dy32, g, mean, rstd,
                           dx0, n0 * D, 1, res0, n0 * D, tw0, n0 * D, dx1, n1 * D, 0, None, 0, None, 0, dg, db)
-        report(tag + ' dx0(acc+res)', rel(dx0, xc.grad[:, :n0] + 1.0 + res0), 1e-4)
-        report(tag + ' dx0 twin', rel(tw0, xc.grad[:, :n0] + 1.0 + res0), 5e-3)
+        report(tag + ' dx0(acc+res)', rel(dx0, xc.grad[:, :n0] + P0 + res0), 1e-4)
+        report(tag + ' dx0 twin', rel(tw0, xc.grad[:, :n0] + P0 + res0), 5e-3)
         if n1:
             report(tag + ' dx1', rel(dx1, xc.grad[:, n0:]), 1e-4)
-        report(tag + ' dgamma', rel(dg, gp.grad), 1e-4)
-        report(tag + ' dbeta', rel(db, bp.grad), 1e-4)
+        report(tag + ' dgamma', rel(dg, pg + gp.grad), 1e-4)
+        report(tag + ' dbeta', rel(db, pb + bp.grad), 1e-4)
+        dx64, bdx = L['dx'].view(B, R, D), L['bdx'].view(B, R, D)
+        acc64 = dx64[:, :n0] + P0.double() + res0.double()
+        bacc = bdx[:, :n0] + kc.out_round(F32) * (dx64[:, :n0].abs() + P0.double().abs() + res0.double().abs())
+        elem(tag + ' dx0(acc+res)', 'layernorm', dx0, acc64, bacc)
+        elem(tag + ' dx0 twin', 'layernorm', tw0, acc64, bacc + kc.U16 * acc64.abs())
+        if n1:
+            elem(tag + ' dx1', 'layernorm', dx1, dx64[:, n0:], bdx[:, n0:] + kc.out_round(F32) * dx64[:, n0:].abs())
+        elem(tag + ' dgamma', 'layernorm', dg, pg.double() + L['dgamma'], L['bdgamma'] + kc.out_round(F32) * (pg.double().abs() + L['dgamma'].abs()))
+        elem(tag + ' dbeta', 'layernorm', db, pb.double() + L['dbeta'], L['bdbeta'] + kc.out_round(F32) * (pb.double().abs() + L['dbeta'].abs()))
+        # the same backward with the statistics deferred (dav_layernorm_bwd_reduce_grouped): into other random prefills
+        pg2, pb2 = kc.prefilled((D,), F32, dev, seed=41), kc.prefilled((D,), F32, dev, seed=42)
+        dg2, db2 = pg2.clone(), pb2.clone()
+        defer = []
+        ops.layernorm_bwd(a0, n0 * D, n0, a1, n1 * D, n1, B, D, dy, dy32, g, mean, rstd,
+                          dx0=kc.poisoned((B, n0, D), F32, dev), dx0_bs=n0 * D, dgamma=dg2, dbeta=db2, defer=defer)
+        ops.layernorm_bwd_reduce_grouped(defer)
+        elem(tag + ' deferred dgamma', 'layernorm', dg2, pg2.double() + L['dgamma'], L['bdgamma'] + kc.out_round(F32) * (pg2.double().abs() + L['dgamma'].abs()))
+        elem(tag + ' deferred dbeta', 'layernorm', db2, pb2.double() + L['dbeta'], L['bdbeta'] + kc.out_round(F32) * (pb2.double().abs() + L['dbeta'].abs()))
 
 
 def _slot_stats(x):
@@ -633,8 +859,8 @@ def ln_fused():
     # 1. stand-alone row statistics + twin (incl. a broadcast source: batch stride 0)
     for (B, rows, D, bs) in [(3, 7, 128, None), (2, 81, 768, None), (4, 16, 512, 0), (2, 5, 1024, None), (64, 49, 768, None)]:
         x = rnd(B if bs is None else 1, rows, D, seed=41) + 0.3
-        tw = torch.empty(B * rows, D, device=dev, dtype=BF16)
-        st = torch.empty(B * rows, D // 64, 2, device=dev)
+        tw = kc.poisoned((B * rows, D), BF16, dev)
+        st = kc.poisoned((B * rows, D // 64, 2), F32, dev)
         ops.rowstats_cast(x, rows * D if bs is None else 0, B, rows, D, tw, st)
         xe = x.expand(B, rows, D).reshape(B * rows, D)
         report(f'rowstats B{B} r{rows} D{D} twin', float((tw.float() - xe.to(BF16).float()).abs().max()), 0.0)
@@ -645,7 +871,7 @@ def ln_fused():
         w = rnd(N, K, scale=0.05, seed=42)
         g, bt = rnd(K, seed=43) * 0.2 + 1, rnd(K, seed=44) * 0.2
         bias = rnd(N, seed=45) if has_b else None
-        wl, c, d = torch.empty(N, K, device=dev, dtype=BF16), torch.empty(N, device=dev), torch.empty(N, device=dev)
+        wl, c, d = kc.poisoned((N, K), BF16, dev), kc.poisoned((N,), F32, dev), kc.poisoned((N,), F32, dev)
         items.append((w, g, bt, bias, wl, c, d))
         wl_ref = (w * g).to(BF16)
         refs.append((wl_ref, wl_ref.double().sum(1), (w.double() * bt.double()).sum(1) + (bias.double() if has_b else 0)))
@@ -694,14 +920,14 @@ def ln_fused():
         w32 = rnd(N, D, scale=0.05, seed=53)            # fp32 master; the un-fused path contracts with its bf16 mirror
         w = w32.to(BF16)
         g, bt, bias = rnd(D, seed=54) * 0.2 + 1, rnd(D, seed=55) * 0.2, rnd(N, seed=56)
-        wl, c, d = torch.empty_like(w), torch.empty(N, device=dev), torch.empty(N, device=dev)
+        wl, c, d = torch.empty_like(w), kc.poisoned((N,), F32, dev), kc.poisoned((N,), F32, dev)
         ops.ln_fold_grouped([(w32, g, bt, bias, wl, c, d)])
         segs = []
         for xs, r in ((x0, r0), (x1, r1)):
             if xs is None:
                 continue
-            tw = torch.empty(B * r, D, device=dev, dtype=BF16)
-            st = torch.empty(B * r, D // 64, 2, device=dev)
+            tw = kc.poisoned((B * r, D), BF16, dev)
+            st = kc.poisoned((B * r, D // 64, 2), F32, dev)
             ops.rowstats_cast(xs, r * D, B, r, D, tw, st)
             segs.append((tw, st, r))
         xc = torch.cat([t for t in (x0, x1) if t is not None], 1)
@@ -710,8 +936,8 @@ def ln_fused():
         pre = ref
         if act == 1:
             ref = torch.nn.functional.gelu(ref)
-        out = torch.empty(M, N, device=dev, dtype=BF16 if c_bf16 else F32)
-        Z = torch.empty(M, N, device=dev, dtype=BF16) if act == 1 else None
+        out = kc.poisoned((M, N), BF16 if c_bf16 else F32, dev)
+        Z = kc.poisoned((M, N), BF16, dev) if act == 1 else None
         lnd = dict(stats=segs[0][1], ln_c=c, eps=eps)
         if len(segs) == 2:
             lnd.update(A2=segs[1][0], stats2=segs[1][1], a_r0=r0, a_r1=r1)
@@ -724,24 +950,24 @@ def ln_fused():
             torch.nn.functional.gelu(xg).sum().backward()
             report(tag + " gelu'twin", float((Z.float() - xg.grad).abs().max()), 2e-2)
         # against the un-fused product path on the same operands (LayerNorm kernel -> bf16 -> GEMM): both are bf16-operand results
-        y = torch.empty(M, D, device=dev, dtype=BF16)
-        mean, rstd = torch.empty(M, device=dev), torch.empty(M, device=dev)
+        y = kc.poisoned((M, D), BF16, dev)
+        mean, rstd = kc.poisoned((M,), F32, dev), kc.poisoned((M,), F32, dev)
         a0, a1 = (x0, x1) if x0 is not None else (x1, None)
         n0, n1 = (r0, r1) if x0 is not None else (r1, 0)
         ops.layernorm_fwd(a0, n0 * D, n0, a1, n1 * D if a1 is not None else 0, n1, B, D, g, bt, eps, y, None, mean, rstd)
-        out2 = torch.empty(M, N, device=dev)
+        out2 = kc.poisoned((M, N), F32, dev)
         ops.gemm_nt(y, w, M, N, D, bias=bias, act=act, C_out=out2)
         report(tag + ' vs unfused (fp32 ref distance ratio)', rel(out, ref) / max(rel(out2, ref), 1e-9), 2.0)
     # 4b. consumer through a row map (the decoder head reads x[:, nF:])
     B, nF, L, D, N = 4, 8, 96, 512, 256
     x = rnd(B, nF + L, D, seed=57)
-    tw, st = torch.empty(B * (nF + L), D, device=dev, dtype=BF16), torch.empty(B * (nF + L), D // 64, 2, device=dev)
+    tw, st = kc.poisoned((B * (nF + L), D), BF16, dev), kc.poisoned((B * (nF + L), D // 64, 2), F32, dev)
     ops.rowstats_cast(x, (nF + L) * D, B, nF + L, D, tw, st)
     w = rnd(N, D, scale=0.05, seed=58)
     g, bt, bias = rnd(D, seed=59) * 0.2 + 1, rnd(D, seed=60) * 0.2, rnd(N, seed=61)
-    wl, c, d = torch.empty(N, D, device=dev, dtype=BF16), torch.empty(N, device=dev), torch.empty(N, device=dev)
+    wl, c, d = kc.poisoned((N, D), BF16, dev), kc.poisoned((N,), F32, dev), kc.poisoned((N,), F32, dev)
     ops.ln_fold_grouped([(w, g, bt, bias, wl, c, d)])
-    out = torch.empty(B * L, N, device=dev)
+    out = kc.poisoned((B * L, N), F32, dev)
     ops.gemm_nt_ln(tw, wl, B * L, N, D, ln=dict(stats=st, ln_c=c, eps=1e-5), a_rowmap=(L, nF + L, nF), bias=d, C_out=out)
     ref = ln(x[:, nF:], (D,), g, bt, 1e-5).reshape(B * L, D) @ w.t() + bias
     report('nt_ln consumer rowmap', rel(out, ref), 6e-3)
@@ -753,7 +979,7 @@ def ln_fused():
         twins = []
         for xx in xs:
             r = xx.shape[1]
-            tw, st = torch.empty(B * r, D, device=dev, dtype=BF16), torch.empty(B * r, D // 64, 2, device=dev)
+            tw, st = kc.poisoned((B * r, D), BF16, dev), kc.poisoned((B * r, D // 64, 2), F32, dev)
             ops.rowstats_cast(xx, r * D, B, r, D, tw, st)
             twins.append((tw, st, r))
         g, bt = rnd(D, seed=33) * 0.1 + 1, rnd(D, seed=34) * 0.1
@@ -766,10 +992,10 @@ def ln_fused():
         (t1, s1, n1) = twins[1] if len(twins) == 2 else (None, None, 0)
         dx0 = torch.full((B, n0, D), 1.0, device=dev)
         res0 = rnd(B, n0, D, seed=37)
-        tw0 = torch.empty(B, n0, D, device=dev, dtype=BF16)
-        dx1 = torch.empty(B, max(n1, 1), D, device=dev)[:, :n1].contiguous() if n1 else None
+        tw0 = kc.poisoned((B, n0, D), BF16, dev)
+        dx1 = kc.poisoned((B, max(n1, 1), D), F32, dev)[:, :n1].contiguous() if n1 else None
         dg, db = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
-        h = torch.empty(B * R, D, device=dev, dtype=BF16)
+        h = kc.poisoned((B * R, D), BF16, dev)
         ops.layernorm_bwd_twin(t0, n0 * D, s0, n0, t1, n1 * D, s1, n1, B, D, eps, dy, dy32, g, bt,
                                dx0, n0 * D, 1, res0, n0 * D, tw0, n0 * D, dx1, n1 * D, 0, None, 0, None, 0, h_out=h, dgamma=dg, dbeta=db)
         tag = f'ln_bwd_twin B{B} {r0}+{r1} D{D}'
@@ -808,12 +1034,12 @@ def misc_kernels():
     img = rnd(B, C, H, W, seed=41)
     L = (H // 16) * (W // 16)
     ids = torch.stack([torch.randperm(L)[:nk] for _ in range(B)]).to(dev).to(torch.int32)
-    A = torch.empty(B * nk, C * 256, device=dev, dtype=BF16)
+    A = kc.poisoned((B * nk, C * 256), BF16, dev)
     ops.patch_gather(img, ids, nk, A)
     cols = img.reshape(B, C, H // 16, 16, W // 16, 16).permute(0, 2, 4, 1, 3, 5).reshape(B, L, C * 256)
     ref = cols.gather(1, ids.long().unsqueeze(-1).expand(-1, -1, C * 256)).reshape(B * nk, -1)
     report('patch_gather', rel(A, ref), 4e-3)
-    A2 = torch.empty(B * L, C * 256, device=dev, dtype=BF16)
+    A2 = kc.poisoned((B * L, C * 256), BF16, dev)
     ops.patch_gather(img, None, L, A2)
     report('patch_gather all', rel(A2, cols.reshape(B * L, -1)), 4e-3)
     # unshuffle
@@ -827,7 +1053,7 @@ def misc_kernels():
     report('unshuffle_fwd', rel(out[:, nF:], ref), 1e-6)
     gx = rnd(B, nF + L, D, seed=45)
     keep = torch.argsort(restore, dim=1)[:, :nk].to(torch.int32)
-    o = torch.empty(B * nk, D, device=dev, dtype=BF16)
+    o = kc.poisoned((B * nk, D), BF16, dev)
     ops.rows_gather_cast(gx, (nF + L) * D, nF, keep, B, nk, D, o)
     report('rows_gather_cast', rel(o.view(B, nk, D), gx[:, nF:].gather(1, keep.long().unsqueeze(-1).expand(-1, -1, D))), 4e-3)
     dpos, dmt = torch.zeros(L, D, device=dev), torch.zeros(D, device=dev)
@@ -847,22 +1073,22 @@ def misc_kernels():
             gsc = torch.tensor(0.7, device=dev)
             pred.grad = None
             (ref * gsc).backward()
-            lp, tm, tr = torch.empty(B * L, device=dev), torch.empty(B * L, device=dev), torch.empty(B * L, device=dev)
-            loss, ms = torch.empty(1, device=dev), torch.empty(1, device=dev)
+            lp, tm, tr = kc.poisoned((B * L,), F32, dev), torch.empty(B * L, device=dev), torch.empty(B * L, device=dev)      # (tm / tr: norm-pix statistics only)
+            loss, ms = kc.poisoned((1,), F32, dev), kc.poisoned((1,), F32, dev)
             ops.patch_mse_fwd(im, pred.detach(), mask, norm, lp, tm, tr, loss, ms)
             report(f'patch_mse fwd C{Cc} norm{int(norm)}', abs(float(loss) - float(ref)) / abs(float(ref)), 1e-5)
-            dp = torch.empty(B * L, P, device=dev, dtype=BF16)
+            dp = kc.poisoned((B * L, P), BF16, dev)
             ops.patch_mse_bwd(im, pred.detach(), mask, tm, tr, ms, gsc, dp)
             report(f'patch_mse bwd C{Cc} norm{int(norm)}', rel(dp.view(B, L, P), pred.grad), 5e-3)
     # pairs
     nv, na, Wd = 3, 2, 64
     Pv, Pa = rnd(B * nv, Wd, seed=48), rnd(B * na, Wd, seed=49)
-    out = torch.empty(B * nv * na, Wd, device=dev, dtype=BF16)
+    out = kc.poisoned((B * nv * na, Wd), BF16, dev)
     ops.pair_expand(Pv, Pa, B, nv, na, Wd, out)
     ref = (Pv.view(B, nv, 1, Wd) + Pa.view(B, 1, na, Wd)).reshape(-1, Wd)
     report('pair_expand', rel(out, ref), 4e-3)
     d = rnd(B * nv * na, Wd, dtype=BF16, seed=50)
-    dPv, dPa = torch.empty(B * nv, Wd, device=dev, dtype=BF16), torch.empty(B * na, Wd, device=dev, dtype=BF16)
+    dPv, dPa = kc.poisoned((B * nv, Wd), BF16, dev), kc.poisoned((B * na, Wd), BF16, dev)
     ops.pair_reduce(d, B, nv, na, Wd, dPv, dPa)
     d4 = d.float().view(B, nv, na, Wd)
     report('pair_reduce v', rel(dPv, d4.sum(2).reshape(-1, Wd)), 4e-3)
@@ -877,23 +1103,35 @@ def misc_kernels():
     ops.rows_axpy(res, yb, sc, Bq, rq, Dq, yb)                      # in place over y
     report('rows_axpy in place', rel(yb, refp), 1e-6)
     gq = rnd(Bq * rq, Dq, seed=63)
-    ob = torch.empty(Bq * rq, Dq, device=dev, dtype=BF16)
+    ob = kc.poisoned((Bq * rq, Dq), BF16, dev)
     ops.rows_scale_cast(gq, sc, Bq, rq, Dq, ob)
     report('rows_scale_cast exact', float((ob != (gq * sc.repeat_interleave(rq)[:, None]).to(BF16)).sum()), 0.0)
     # casts / norm / adamw
     x = rnd(1000, 77, seed=51)
-    y = torch.empty(1000, 77, device=dev, dtype=BF16)
+    y = kc.poisoned((1000, 77), BF16, dev)
     ops.cast_bf16(x, y)
     report('cast_bf16 exact', float((y != x.to(BF16)).sum()), 0.0)
     for shape in [(64, 16, 768), (3, 5, 128), (1, 4)]:
         a, b = rnd(*shape, seed=91), rnd(*shape, seed=92)
         o32, ob = ops.add_cast(a, b)
         report(f'add_cast {shape}', float((o32 != a + b).sum()) + float((ob != (a + b).to(BF16)).sum()), 0.0)
-    yt = torch.empty(77, 1000, device=dev, dtype=BF16)
+    yt = kc.poisoned((77, 1000), BF16, dev)
     ops.cast_transpose_bf16(x, yt)
     report('cast_transpose exact', float((yt != x.t().to(BF16)).sum()), 0.0)
+    # grouped cast-transpose (dav_cast_transpose_grouped): every y bit-exact round-to-nearest-even of x^T, each inside its own guards
+    pairs, gs = [], []
+    for i, (R, Cc) in enumerate([(768, 2304), (3072, 768), (64, 192), (128, 64)]):
+        xi = rnd(R, Cc, seed=200 + i)
+        g = kc.Guarded(Cc, R, BF16, device=dev)
+        pairs.append((xi, g.t))
+        gs.append(g)
+    ops.cast_transpose_grouped(pairs)
+    for (xi, yi), g in zip(pairs, gs):
+        n_bad = int((yi.view(torch.int16) != xi.t().contiguous().to(BF16).view(torch.int16)).sum())
+        report(f'cast_transpose_grouped {tuple(xi.shape)} bit-exact', float(n_bad), 0.0)
+        guard(f'cast_transpose_grouped {tuple(xi.shape)}', g)
     flat = rnd(1234567, seed=52)
-    out, ws = torch.empty(1, device=dev), torch.empty(1024, device=dev)
+    out, ws = kc.poisoned((1,), F32, dev), torch.empty(1024, device=dev)
     ops.l2norm(flat, out, ws, 0.5)
     report('l2norm', abs(float(out) - 0.5 * float(flat.double().norm())) / float(flat.double().norm()), 1e-6)
     n = 100036                    # the flat buffers' contract: length and segment boundaries multiples of 4, 16-byte aligned
@@ -901,7 +1139,7 @@ def misc_kernels():
     pr = p0.clone().requires_grad_(True)
     opt = torch.optim.AdamW([{'params': [pr], 'weight_decay': 0.05}], lr=1e-2, betas=(0.9, 0.95))
     p, m, v = p0.clone(), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    pb = torch.empty(n, device=dev, dtype=BF16)
+    pb = kc.poisoned((n,), BF16, dev)
     seg = torch.tensor([40000, n], device=dev, dtype=torch.int64)
     hyper = torch.tensor([1e-2, 0.05, 1e-2, 0.05], device=dev)
     for step in range(1, 4):
@@ -922,9 +1160,9 @@ def misc_kernels():
     # zero-fills the gradients and still reports sum(g^2)
     bc = torch.tensor([1 - 0.9 ** 4, math.sqrt(1 - 0.95 ** 4)], device=dev)
     one, nan, inf = torch.tensor([2.5], device=dev), torch.tensor([float('nan')], device=dev), torch.tensor([float('inf')], device=dev)
-    gn, ws = torch.empty(1, device=dev), torch.empty(1024, device=dev)
+    gn, ws = kc.poisoned((1,), F32, dev), torch.empty(1024, device=dev)
     ops.l2norm(g0, gn, ws, 1.0)
-    sc, bad = torch.empty(1, device=dev), torch.zeros(1, device=dev, dtype=torch.int32)
+    sc, bad = kc.poisoned((1,), F32, dev), torch.zeros(1, device=dev, dtype=torch.int32)
     clip = 0.25 * float(gn)
     ops.step_guard(one, one, gn, clip, 1.0, sc, bad)
     report('step_guard clip factor', abs(float(sc) - clip / (float(gn) + 1e-6)), 1e-7)
@@ -960,6 +1198,7 @@ def main():
         if flt in fn.__name__:
             fn()
     bad = [r for r in RESULTS if not r[3]]
+    print('worst err / bound per family:', {k: float(f'{v:.3e}') for k, v in sorted(kc.RATIOS.items())})
     print(f'\n{len(RESULTS) - len(bad)}/{len(RESULTS)} checks passed')
     for r in bad:
         print('  FAILED:', r[0], r[1])

@@ -1,0 +1,264 @@
+"""Elementwise checks of kernel outputs (used by tests/gpu_selfcheck.py and tests/gpu_fuzz.py; device-agnostic, its own tests
+run on the CPU: tests/test_kcheck.py).
+
+A relative-L2 figure over a whole tensor hides a localized error: one wrong row among thousands, one tile off by 10 %, one
+tile never written whose memory still holds an earlier correct answer.  So every output is judged three ways:
+
+* it starts POISONED (NaN / an integer sentinel) when the contract says the kernel writes it, or PREFILLED with random values
+  when the contract says it accumulates — an element the kernel skips cannot pass;
+* every element must satisfy |got - ref| <= bound, the bound propagated from the magnitudes of the operands in float64 through
+  the same formula (``within`` and the ``*_bound`` helpers below) — no fixed per-shape tolerance;
+* the output sits in a GUARDED buffer: guard bands in front and behind and the padding of its row stride hold a fixed byte
+  pattern that must come back bit-identical (``Guarded``) — a store past N, past the last row or into a neighbour shows.
+"""
+import math
+
+import torch
+
+GUARD_BYTES = 256                 # each guard band (a multiple of 16: the view keeps the 16-byte alignment of the allocation)
+GUARD_BYTE = 0xA5                 # fill pattern of every byte outside the view (fp32 0xA5A5A5A5 / bf16 0xA5A5: finite, never a result)
+INT_POISON = -0x5A5A5A5B          # sentinel of int outputs
+U32 = 2.0 ** -24                  # unit roundoff of fp32
+U16 = 2.0 ** -8                   # unit roundoff of bf16 (8 significant bits): EXACTLY the worst case of one rounding, no slack —
+                                  # the bf16-output bounds hold because the accumulation term adds to it; never lower this
+
+# one constant per family, fixed here (never per shape); see the *_bound helpers for what each multiplies
+C_GEMM = 1.0                      # fp32 accumulation over K: the classical K * u * |A||B|^T
+C_ATTN = 4.0                      # P (and dS) rounded to bf16 before their products, plus the exp / max-shift of the softmax
+GELU_ABS = 5e-7                   # erf approximation of the GELU epilogue (|err| <= 1.5e-7, gpu_selfcheck.gemm_nt) + its fp32 evaluation
+
+RATIOS = {}                       # family -> worst err / bound seen (printed per family on the device)
+
+
+def poisoned(shape, dtype, device='cpu'):
+    """An output the kernel is contracted to WRITE: NaN (floating) or INT_POISON everywhere."""
+    if dtype.is_floating_point:
+        return torch.full(shape, float('nan'), dtype=dtype, device=device)
+    return torch.full(shape, INT_POISON, dtype=dtype, device=device)
+
+
+def prefilled(shape, dtype=torch.float32, device='cpu', seed=0):
+    """An output the kernel is contracted to ACCUMULATE into: random values (the check is then out == prefill + result)."""
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    return torch.randn(*shape, generator=g).to(device=device, dtype=dtype)
+
+
+class Guarded:
+    """A [rows, cols] output as a view with row stride ``ld`` inside a larger buffer: GUARD_BYTES of pattern in front, the padding
+    columns of every row and GUARD_BYTES behind.  ``fill``: 'poison' (written outputs), 'zero', a number, or a tensor to copy in
+    (accumulated outputs)."""
+
+    def __init__(self, rows, cols, dtype, ld=None, device='cpu', fill='poison'):
+        ld = cols if ld is None else ld
+        assert ld >= cols
+        es = torch.tensor([], dtype=dtype).element_size()
+        assert GUARD_BYTES % es == 0
+        self.rows, self.cols, self.ld, self.dtype = rows, cols, ld, dtype
+        self.lead = GUARD_BYTES // es
+        n = self.lead + rows * ld + self.lead
+        self.flat = torch.empty(n, dtype=dtype, device=device)
+        self.flat.view(torch.uint8).fill_(GUARD_BYTE)
+        self.t = self.flat[self.lead:self.lead + rows * ld].view(rows, ld)[:, :cols]
+        self.set(fill)
+        inside = torch.zeros(n, dtype=torch.bool, device=device)
+        inside[self.lead:self.lead + rows * ld].view(rows, ld)[:, :cols] = True
+        self._outside = ~inside
+
+    def set(self, fill):
+        if isinstance(fill, torch.Tensor):
+            self.t.copy_(fill.reshape(self.rows, self.cols))
+        elif fill == 'poison':
+            self.t.copy_(poisoned((self.rows, self.cols), self.dtype, self.t.device))
+        elif fill == 'zero':
+            self.t.zero_()
+        else:
+            self.t.fill_(fill)
+        return self
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def stray(self):
+        """(number of elements outside the view whose bytes changed, description of the first one or '')"""
+        b = self.flat.view(torch.uint8).view(self.flat.numel(), -1)
+        changed = (b != GUARD_BYTE).any(1) & self._outside
+        n = int(changed.sum())
+        if not n:
+            return 0, ''
+        i = int(changed.nonzero()[0, 0])
+        if i < self.lead:
+            where = f'leading guard, {self.lead - i} elements in front of the view'
+        elif i >= self.lead + self.rows * self.ld:
+            where = f'trailing guard, element {i - self.lead - self.rows * self.ld} behind the view'
+        else:
+            r, c = divmod(i - self.lead, self.ld)
+            where = f'row {r} padding column {c} (cols {self.cols}, ld {self.ld})'
+        return n, where
+
+
+def changed(t, before, mask=None):
+    """Elements of ``t`` whose BITS differ from the snapshot ``before`` (only where ``mask``: a bool over the leading dims, e.g.
+    the rows a row map skips, the context rows of a fused buffer).  Returns (count, flat index of the first one or -1)."""
+    es = t.element_size()
+    a = t.contiguous().view(torch.uint8).view(-1, es)
+    b = before.contiguous().view(torch.uint8).view(-1, es)
+    diff = (a != b).any(1).view(t.shape)
+    if mask is not None:
+        diff = diff & mask.view(tuple(mask.shape) + (1,) * (t.dim() - mask.dim())).expand_as(diff)
+    n = int(diff.sum())
+    return n, (int(diff.flatten().nonzero()[0, 0]) if n else -1)
+
+
+def tile_of(idx, shape):
+    """'[r, c] tile128 (r//128, c//128) tile256 (...)' of a flat index into ``shape`` (the last two dims are the matrix)."""
+    pos = []
+    for s in reversed(shape):
+        pos.append(idx % s)
+        idx //= s
+    pos = pos[::-1]
+    if len(pos) >= 2:
+        r, c = pos[-2], pos[-1]
+        return f'{pos} tile128 ({r // 128}, {c // 128}) tile256 ({r // 256}, {c // 256})'
+    return f'{pos}'
+
+
+def within(got, ref, bound, tag=''):
+    """Elementwise |got - ref| <= bound in float64; a non-finite ``got`` always fails.  Returns (ok, worst err / bound, message);
+    the message names the worst element and its 128- and 256-tile."""
+    g = got.detach().double()
+    r = ref.detach().double().expand_as(g)
+    b = torch.as_tensor(bound, dtype=torch.float64, device=g.device).expand_as(g)
+    err = (g - r).abs()
+    ratio = torch.where(b > 0, err / b.clamp_min(1e-300), torch.where(err > 0, float('inf'), 0.0))
+    ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, float('inf')))
+    if ratio.numel() == 0:
+        return True, 0.0, ''
+    worst = float(ratio.max())
+    ok = worst <= 1.0
+    if ok:
+        return True, worst, ''
+    i = int(ratio.flatten().argmax())
+    nbad = int((ratio > 1.0).sum())
+    msg = (f'{tag}: {nbad} of {g.numel()} elements outside the bound; worst at {tile_of(i, tuple(g.shape))}: '
+           f'got {float(g.flatten()[i]):.6g} ref {float(r.flatten()[i]):.6g} bound {float(b.flatten()[i]):.3g}')
+    return False, worst, msg
+
+
+def note(family, ratio):
+    if math.isfinite(ratio):
+        RATIOS[family] = max(RATIOS.get(family, 0.0), ratio)
+
+
+# ---- bounds ---------------------------------------------------------------------------------------------------------------
+
+def out_round(dtype):
+    """relative rounding allowance of the stored value: bf16 2^-8, fp32 2^-22 (a few roundings of the epilogue's adds)"""
+    return U16 if dtype == torch.bfloat16 else 4 * U32
+
+
+def gemm_scale(A, B):
+    """|A| |B|^T in float64 for A [M, K], B [N, K]"""
+    return A.detach().double().abs() @ B.detach().double().abs().t()
+
+
+def gemm_bound(A, B, ref, out_dtype, alpha=1.0, c=C_GEMM):
+    """C = alpha * A . B^T (+ epilogue terms that enter through |ref|): c * 2^-24 * K * |alpha| |A||B|^T + r_out |ref|"""
+    K = A.shape[-1]
+    return c * U32 * K * abs(alpha) * gemm_scale(A, B) + out_round(out_dtype) * ref.detach().double().abs()
+
+
+def gelu_bound(pre_bound, ref, out_dtype):
+    """GELU epilogue: |gelu'| <= 1.13 carries the pre-activation bound; + 1e-6 |ref| + the erf approximation"""
+    return 1.13 * pre_bound + (1e-6 + out_round(out_dtype)) * ref.detach().double().abs() + GELU_ABS
+
+
+def dgelu_bound(pre_bound, ref, out_dtype):
+    """GELU' twin: |gelu''| <= 0.8 carries the pre-activation bound"""
+    return 0.8 * pre_bound + (1e-6 + out_round(out_dtype)) * ref.detach().double().abs() + GELU_ABS
+
+
+def softmax64(q, k, scale, bias=None):
+    """float64 P = softmax(scale q k^T (+ bias)) of [.., N, d] operands, and the float64 logits"""
+    s = (q.detach().double() @ k.detach().double().transpose(-2, -1)) * scale
+    if bias is not None:
+        s = s + bias.double()
+    return s.softmax(-1), s
+
+
+def attn_bounds(q, k, v, dO, O, scale, keep=None, up=U16, r_out=U16, c=C_ATTN, bias=None):
+    """Float64 references and elementwise bounds of attention forward and backward ([B, H, N, d] operands, keep: the keep mask
+    already divided by the keep probability, or None).  P is rounded to bf16 (relative ``up``) before P.V, dS before dS.K / dS^T.Q:
+      O   : c up (P~|V|) + r_out |O|                      (P~ = P * keep)
+      dV  : c up (P~^T |dO|) + r_out |dV|
+      dQ  : scale c up (P o (keep |dO||V|^T + Dabs)) |K| + r_out |dQ|,  dK likewise with |Q|
+    where Dabs = sum |dO| |O| bounds the row term Delta = sum dO O (the kernel forms it from its own rounded O)."""
+    P, s = softmax64(q, k, scale, bias)
+    q64, k64, v64 = (t.detach().double() for t in (q, k, v))
+    Pk = P if keep is None else P * keep.double()
+    O64 = Pk @ v64
+    lse = torch.logsumexp(s, -1)
+    b_O = c * up * (Pk @ v64.abs()) + r_out * O64.abs()
+    b_lse = 1e-5 * (1.0 + lse.abs() + s.abs().amax(-1))
+    out = dict(P=P, O=O64, lse=lse, bO=b_O, blse=b_lse)
+    if dO is None:
+        return out
+    d64 = dO.detach().double()
+    dP = d64 @ v64.transpose(-2, -1)
+    if keep is not None:
+        dP = dP * keep.double()
+    Delta = (d64 * O64).sum(-1, keepdim=True)
+    dS = P * (dP - Delta)
+    dq = scale * dS @ k64
+    dk = scale * dS.transpose(-2, -1) @ q64
+    dv = Pk.transpose(-2, -1) @ d64
+    Dabs = (d64.abs() * O.detach().double().abs()).sum(-1, keepdim=True) + (d64.abs() * O64.abs()).sum(-1, keepdim=True)
+    mag = d64.abs() @ v64.abs().transpose(-2, -1)
+    if keep is not None:
+        mag = mag * keep.double()
+    S = P * (mag + Dabs)
+    out.update(dq=dq, dk=dk, dv=dv,
+               bdq=scale * c * up * (S @ k64.abs()) + r_out * dq.abs(),
+               bdk=scale * c * up * (S.transpose(-2, -1) @ q64.abs()) + r_out * dk.abs(),
+               bdv=c * up * (Pk.transpose(-2, -1) @ d64.abs()) + r_out * dv.abs(),
+               dS=dS, bdS=c * up * S + 4 * U32 * dS.abs())
+    return out
+
+
+def gang(probs):
+    """dav_gemm_tn_gang_bf16 (through ops.gemm_tn_gang) with its workspace filled with 0xFF bytes: the header only says caller-owned,
+    so the kernel must initialise its tickets itself on every call"""
+    from deepavfusion_amd import ops
+    ops.gemm_tn_gang(probs, workspace_fill=0xFF)
+    torch.cuda.synchronize()
+
+
+C_LN = 64.0                       # LayerNorm: fp32 mean / variance / rstd over D <= a few thousand columns, then per-element products
+
+
+def ln_bounds(x, gamma, beta, eps, dy=None):
+    """Float64 LayerNorm over the last dim (rows [.., D]) and elementwise bounds from the magnitudes:
+      y      : C_LN u (|gamma| (|xhat| + rstd mean|x|) + |beta|)                       (xhat = (x - mean) rstd)
+      dx     : C_LN u rstd (|g| + mean|g| + |xhat| mean|g xhat|) (1 + |xhat|)           (g = dy gamma)
+      dgamma : u (rows sum|dy xhat| + C_LN sum |dy| (1 + |xhat|) (1 + rstd mean|x|)),  dbeta: u rows sum|dy|"""
+    x64 = x.detach().double()
+    D = x64.shape[-1]
+    mean = x64.mean(-1, keepdim=True)
+    rstd = (((x64 - mean) ** 2).mean(-1, keepdim=True) + eps).rsqrt()
+    xh = (x64 - mean) * rstd
+    g64, b64 = gamma.detach().double(), beta.detach().double()
+    stat = 1 + rstd * x64.abs().mean(-1, keepdim=True)
+    out = dict(y=xh * g64 + b64, mean=mean.squeeze(-1), rstd=rstd.squeeze(-1),
+               by=C_LN * U32 * (g64.abs() * (xh.abs() + stat) + b64.abs()))
+    if dy is None:
+        return out
+    d64 = dy.detach().double()
+    gd = d64 * g64
+    dx = rstd * (gd - gd.mean(-1, keepdim=True) - xh * (gd * xh).mean(-1, keepdim=True))
+    mag = rstd * (gd.abs() + gd.abs().mean(-1, keepdim=True) + xh.abs() * (gd * xh).abs().mean(-1, keepdim=True))
+    d2, x2 = d64.reshape(-1, D), xh.reshape(-1, D)
+    rows = d2.shape[0]
+    out.update(dx=dx, bdx=C_LN * U32 * mag * (1 + xh.abs()) * stat,
+               dgamma=(d2 * x2).sum(0), dbeta=d2.sum(0),
+               bdgamma=U32 * (rows * (d2 * x2).abs().sum(0) + C_LN * (d2.abs() * (1 + x2.abs()) * stat.reshape(-1, 1)).sum(0)),
+               bdbeta=U32 * rows * d2.abs().sum(0))
+    return out

@@ -369,6 +369,17 @@ def test_error_codes_for_dtype_alignment_and_workspace():
     assert lib.dav_dropout_rows(*dr) == -1                                   # a mask needs its scale
     dr[4], dr[3] = C.c_float(1.25), p(8192 + 1)
     assert lib.dav_dropout_rows(*dr) == -5
+    # four elements per access: res and fp32 in / out as float4 (16 bytes), bf16 in / out 8 bytes (each case misaligns exactly one
+    # pointer by 8 — or a bf16 one by 4 — and every other argument is valid)
+    for idx, f32_flag, addr in ((2, None, 16384 + 8),                       # res
+                                (0, 1, 4096 + 8), (9, 10, 12288 + 8),        # fp32 in, fp32 out
+                                (0, None, 4096 + 4), (9, None, 12288 + 4)):  # bf16 in / out below 8 bytes
+        a = list(dr)
+        a[3] = p(8192)
+        if f32_flag is not None:
+            a[f32_flag] = C.c_int(1)
+        a[idx] = p(addr)
+        assert lib.dav_dropout_rows(*a) == -5, (idx, f32_flag)
 
 
 def test_written_first_contribution_bookkeeping(monkeypatch):

@@ -1099,6 +1099,8 @@ def test_written_first_gradients_equal_accumulated_ones(monkeypatch):
         torch.cuda.synchronize()
         finals.append(opt.flat.flat_p.clone())
         losses.append(run)
+        names = {id(p): n for n, p in model.named_parameters()}
+        layout = [(names[id(p)], o, p.numel()) for p, o in zip(opt.flat.params, opt.flat.offsets)]
     n_linear = sum(1 for n, p in model.named_parameters() if p.ndim == 2 and p.requires_grad)
     assert kept[0] > n_linear // 2 and kept[1] == 0, (kept, n_linear)
     assert all(np.isfinite(losses[0])) and losses[0][-1] < losses[0][0]
@@ -1111,8 +1113,29 @@ def test_written_first_gradients_equal_accumulated_ones(monkeypatch):
     # rounding noise on (near-)zero gradients — key biases, the pair attention's k projection under a near-uniform softmax — into
     # lr-sized steps of either sign: which sign is decided by the last bit, so the figure moves with any change of rounding anywhere
     # upstream (1.1e-4 .. 3.9e-4 across the builds of rounds 5-6, all of it in those parameters: tools/runs_r06/wf_probe.py); a LOST
-    # contribution would show at >= 4e-3
-    assert rel(finals[0], finals[1]) < 1e-3
+    # contribution would show at >= 4e-3.  So 1e-3 holds for those parameters only — the KEY part of the biases that make keys (the
+    # middle third of a fused qkv bias, the first half of a fused kv bias, the pair attention's k bias) and the pair attention's k
+    # weight — and everything else, query and value biases included, stays at 2e-4.
+    def key_part(n, sz):
+        if n.endswith('.qkv.bias'):
+            return sz // 3, 2 * sz // 3
+        if n.endswith('.kv.bias'):
+            return 0, sz // 2
+        if n.endswith('.attn.k.bias') or n.endswith('.attn.k.weight'):
+            return 0, sz
+        return 0, 0
+    noisy = torch.zeros(finals[0].numel(), dtype=torch.bool, device=finals[0].device)
+    for n, o, sz in layout:
+        lo, hi = key_part(n, sz)
+        noisy[o + lo:o + hi] = True
+    owned = torch.zeros_like(noisy)
+    for n, o, sz in layout:
+        owned[o:o + sz] = True
+    quiet = owned & ~noisy
+    assert bool(noisy.any()) and bool(quiet.any())
+    assert rel(finals[0][quiet], finals[1][quiet]) < 2e-4
+    # (the noisy set is measured as before: its share of the difference against the norm of ALL parameters)
+    assert float((finals[0][noisy] - finals[1][noisy]).double().norm() / finals[1].double().norm()) < 1e-3
 
 
 def test_trainer_skip_grad_drops_an_outlier_micro_step():
