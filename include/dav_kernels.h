@@ -168,7 +168,8 @@ int dav_attn_bwd_ctx(const void* Q, const void* K, const void* V, const void* O,
  * kernels with an additive logit bias.  bias [bias_nb][H][Nq][bias_ld] fp32 in LOG2 units (natural value x log2 e), zero
  * padded to bias_ld >= Nk rounded up to 32; batch element b uses table b % bias_nb (the shift mask differs per window,
  * :75-78).  Backward: dS [B][H][Nq][bias_ld] (optional) receives the gradient of the biased logits in natural units — what
- * dav_relpos_bias_bwd reduces into the relative-position table's gradient. */
+ * dav_relpos_bias_bwd reduces into the relative-position table's gradient; its columns [Nk, Nk rounded up to 32) receive finite
+ * values (the zero-padded keys' share, to be ignored), the columns beyond are left untouched (the fp32 twin writes [0, Nk) only). */
 int dav_attn_bias_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int Nq, int Nk, int dqk,
                       int dv, long q_bs, int q_rs, long k_bs, int k_rs, long v_bs, int v_rs, long o_bs, int o_rs, float scale,
                       const float* bias, int bias_nb, int bias_ld, hipStream_t stream);
@@ -199,7 +200,8 @@ int dav_attn_drop_bwd(const void* Q, const void* K, const void* V, const void* O
  * tokens], B * nW of them.  rows[w * A + i] = token (0-based, within the L token rows) at slot i of window w after the cyclic
  * shift (torch.roll + timm window_partition, models/swin.py:172-179); inv = its inverse permutation.
  * dav_window_unfold: sequences <- rows (the fusion rows repeated per window and scaled by fusion_scale; models/swin.py:183-185;
- *   with fusion_scale = 1 / nW also the backward of the fold's mean).  src fp32 or bf16, out bf16 or fp32.
+ *   with fusion_scale = 1 / nW also the backward of the fold's mean).  src fp32 -> out bf16 or fp32, src bf16 -> out bf16
+ *   (bf16 -> fp32 returns DAV_ERR_DTYPE).
  * dav_window_fold: rows <- sequences (+ res): token rows through inv (window_reverse + roll back, :191-197), fusion rows =
  *   fusion_scale x the sum over the windows (1 / nW: the mean of :199; 1: the backward of the unfold's repeat). */
 int dav_window_unfold(const void* src, int src_is_bf16, const int* rows, int B, int nW, int A, int nF, int L, int C,
@@ -208,7 +210,8 @@ int dav_window_fold(const float* t, const int* inv, const float* res, int B, int
                     float fusion_scale, float* out, hipStream_t stream);
 /* out[w][h][q][k] = mul * (table[index[q * A + k]][h] + mask[w][q][k]) for q, k < A, 0 elsewhere ([nb][H][N][ld]; mask NULL
  * for unshifted blocks, then nb = 1): models/swin.py:49-53 + :66-78 (the reference pads both with zeros to the N = A + nF
- * sequence).  dav_relpos_bias_bwd: dtable[e][h] += sum over the Bw sequences and the (q, k) with index == e of dS. */
+ * sequence).  dav_relpos_bias_bwd: dtable[e][h] += sum over the Bw sequences and the (q, k) with index == e of dS; A * A <= 1024
+ * (windows up to 5 x 5; a larger A returns DAV_ERR_SHAPE). */
 int dav_relpos_bias_build(const float* table, const int* index, const float* mask, int nb, int H, int A, int N, int ld, float mul,
                           float* out, hipStream_t stream);
 int dav_relpos_bias_bwd(const float* dS, const int* index, int Bw, int H, int A, int N, int ld, int T, float* dtable,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised shape fuzz of the C-ABI kernels against torch fp32 references (companion of tests/gpu_selfcheck.py, which uses
-fixed shape lists).  Usage: python tests/gpu_fuzz.py [seed] [n_gemm] [n_attn] [n_ln] [n_gang]"""
+fixed shape lists).  Usage: python tests/gpu_fuzz.py [seed] [n_gemm] [n_attn] [n_ln] [n_gang]  (n_ln also counts the row-mover shapes)"""
 import os
 import random
 import sys
@@ -39,6 +39,14 @@ def elem(tag, family, got, ref, bound):
     kc.note(family, ratio)
     if not ok:
         FAILS.append((tag + ' elementwise', ratio, 1.0))
+        print(f'FAIL {msg}', flush=True)
+
+
+def same(tag, got, ref):
+    """bit-exact (tests/kcheck.py exact)"""
+    nd, msg = kc.exact(got, ref, tag)
+    if nd:
+        FAILS.append((tag + ' bit-exact', nd, 0))
         print(f'FAIL {msg}', flush=True)
 
 
@@ -232,23 +240,104 @@ def fuzz_ln(rng, n):
         eps = rng.choice([1e-5, 1e-6])
         ref = torch.nn.functional.layer_norm(xc, (D,), gp, bp, eps)
         R = r0 + r1
-        y, y32 = torch.empty(B * R, D, device=dev, dtype=BF16), torch.empty(B * R, D, device=dev)
-        mean, rstd = torch.empty(B * R, device=dev), torch.empty(B * R, device=dev)
+        y, y32 = kc.poisoned((B * R, D), BF16, dev), kc.poisoned((B * R, D), F32, dev)
+        mean, rstd = kc.poisoned((B * R,), F32, dev), kc.poisoned((B * R,), F32, dev)
         a0, a1, n0, n1 = (x0, x1, r0, r1) if x0 is not None else (x1, None, r1, 0)
         ops.layernorm_fwd(a0, n0 * D, n0, a1, n1 * D, n1, B, D, g, bt, eps, y, y32, mean, rstd)
         tag = f'ln B{B} {r0}+{r1} D{D}'
         check(tag + ' fwd', rel(y32, ref.view(-1, D)), 2e-5)
         dy = torch.randn(B * R, D, device=dev).to(BF16)
         ref.backward(dy.view(B, R, D).float())
-        dx0 = torch.zeros(B, n0, D, device=dev)
-        dx1 = torch.zeros(B, max(n1, 1), D, device=dev) if n1 else None
-        dg, db = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
+        Lb = kc.ln_bounds(xc.view(-1, D), g, bt, eps, dy.double())
+        elem(tag + ' fwd32', 'fuzz_ln', y32, Lb['y'], Lb['by'] + kc.out_round(F32) * Lb['y'].abs())
+        elem(tag + ' fwd16', 'fuzz_ln', y, Lb['y'], Lb['by'] + kc.U16 * Lb['y'].abs())
+        elem(tag + ' mean', 'fuzz_ln', mean, Lb['mean'], kc.C_LN * kc.U32 * xc.view(-1, D).double().abs().mean(-1))
+        elem(tag + ' rstd', 'fuzz_ln', rstd, Lb['rstd'], kc.C_LN * kc.U32 * Lb['rstd'])
+        dx0 = kc.poisoned((B, n0, D), F32, dev)                         # written (acc0 = 0)
+        dx1 = kc.poisoned((B, max(n1, 1), D), F32, dev) if n1 else None
+        pg, pb = kc.prefilled((D,), F32, dev, seed=2 * it), kc.prefilled((D,), F32, dev, seed=2 * it + 1)   # dgamma / dbeta +=
+        dg, db = pg.clone(), pb.clone()
         ops.layernorm_bwd(a0, n0 * D, n0, a1, n1 * D, n1, B, D, dy, None, g, mean, rstd, dx0=dx0, dx0_bs=n0 * D, dx1=dx1,
                           dx1_bs=n1 * D, dgamma=dg, dbeta=db)
         dxc = torch.cat([t for t in (dx0, dx1) if t is not None], 1)
         check(tag + ' dx', rel(dxc, xc.grad), 3e-5)
-        check(tag + ' dgamma', rel(dg, gp.grad), 3e-4)
-        check(tag + ' dbeta', rel(db, bp.grad), 3e-4)
+        check(tag + ' dgamma', rel(dg - pg, gp.grad), 3e-4)
+        check(tag + ' dbeta', rel(db - pb, bp.grad), 3e-4)
+        dx64, bdx = Lb['dx'].view(B, R, D), Lb['bdx'].view(B, R, D)
+        elem(tag + ' dx', 'fuzz_ln', dxc, dx64, bdx + kc.out_round(F32) * dx64.abs())
+        elem(tag + ' dgamma', 'fuzz_ln', dg, pg.double() + Lb['dgamma'], Lb['bdgamma'] + kc.out_round(F32) * (pg.double().abs() + Lb['dgamma'].abs()))
+        elem(tag + ' dbeta', 'fuzz_ln', db, pb.double() + Lb['dbeta'], Lb['bdbeta'] + kc.out_round(F32) * (pb.double().abs() + Lb['dbeta'].abs()))
+
+
+def fuzz_rows(rng, n):
+    """Random row-mover shapes: unshuffle_fwd (the nF leading rows untouched) / _bwd_reduce (into random prefills),
+    rows_gather_cast (ids, and ids = None with row_off), pair_expand / _reduce and patch_gather — copies and single roundings
+    bit-exact, sums inside kcheck.sum_bound, every 2-D output guarded."""
+    for it in range(n):
+        B, L = rng.randint(1, 6), rng.randint(1, 400)
+        nk, D, nF = rng.randint(1, L), 4 * rng.randint(1, 200), rng.choice([0, 1, 3, rng.randint(0, 40)])
+        tag = f'rows #{it} B{B} L{L} nk{nk} D{D} nF{nF}'
+        restore = torch.stack([torch.randperm(L, device=dev) for _ in range(B)])
+        r32 = restore.to(torch.int32)
+        emb, mt, pos = torch.randn(B * nk, D, device=dev), torch.randn(D, device=dev), torch.randn(L, D, device=dev)
+        g = kc.Guarded(B * (nF + L), D, F32, device=dev)
+        before = g.t.clone()
+        out = g.t.view(B, nF + L, D)
+        ops.unshuffle_fwd(emb, mt, pos, r32, B, L, nk, D, out, (nF + L) * D, nF)
+        full = torch.cat([emb.view(B, nk, D), mt.view(1, 1, D).expand(B, L - nk, D)], 1)
+        same(tag + ' unshuffle_fwd', out[:, nF:], full.gather(1, restore.unsqueeze(-1).expand(-1, -1, D)) + pos)
+        lead = torch.zeros(B, nF + L, dtype=torch.bool, device=dev)
+        lead[:, :nF] = True
+        nch, i = kc.changed(g.t, before, lead.view(-1))
+        if nch:
+            FAILS.append((tag + ' unshuffle_fwd leading rows untouched', nch, 0))
+            print(f'FAIL {tag} unshuffle_fwd: {nch} elements of the {nF} leading rows changed, first at {kc.tile_of(i, tuple(g.t.shape))}', flush=True)
+        guard(tag + ' unshuffle_fwd', g)
+        gx = torch.randn(B, nF + L, D, device=dev)
+        keep = torch.argsort(restore, dim=1)[:, :nk].to(torch.int32)
+        for sel, m, want in ((keep, nk, gx[:, nF:].gather(1, keep.long().unsqueeze(-1).expand(-1, -1, D))), (None, L, gx[:, nF:])):
+            g = kc.Guarded(B * m, D, BF16, device=dev)
+            ops.rows_gather_cast(gx, (nF + L) * D, nF, sel, B, m, D, g.t)
+            same(f'{tag} rows_gather_cast {"ids" if sel is not None else "row_off"}', g.t.view(B, m, D), want.to(BF16))
+            guard(f'{tag} rows_gather_cast', g)
+        gp, gm = kc.Guarded(L, D, F32, device=dev, fill=kc.prefilled((L, D), seed=it)), kc.Guarded(1, D, F32, device=dev, fill=kc.prefilled((1, D), seed=it + 1))
+        pp, pm = gp.t.double(), gm.t.double()
+        ops.unshuffle_bwd_reduce(gx, (nF + L) * D, nF, r32, B, L, nk, D, gp.t, gm.t)
+        g64, m64 = gx[:, nF:].double(), (restore >= nk).double().unsqueeze(-1)
+        wp, wm = pp + g64.sum(0), pm + (g64 * m64).sum((0, 1))
+        elem(tag + ' dpos +=', 'fuzz_rows', gp.t, wp, kc.sum_bound(pp.abs() + g64.abs().sum(0), B + 1, wp))
+        elem(tag + ' dmask_token +=', 'fuzz_rows', gm.t, wm, kc.sum_bound(pm.abs() + (g64 * m64).abs().sum((0, 1)), B * L + 1, wm))
+        guard(tag + ' dpos', gp)
+        guard(tag + ' dmask_token', gm)
+        # pairs
+        nv, na, Wd = rng.randint(1, 12), rng.randint(1, 12), 4 * rng.randint(1, 200)
+        ptag = f'pairs #{it} B{B} {nv}x{na}x{Wd}'
+        Pv, Pa = torch.randn(B * nv, Wd, device=dev), torch.randn(B * na, Wd, device=dev)
+        g = kc.Guarded(B * nv * na, Wd, BF16, device=dev)
+        ops.pair_expand(Pv, Pa, B, nv, na, Wd, g.t)
+        same(ptag + ' pair_expand', g.t, (Pv.view(B, nv, 1, Wd) + Pa.view(B, 1, na, Wd)).reshape(-1, Wd).to(BF16))
+        guard(ptag + ' pair_expand', g)
+        d = torch.randn(B * nv * na, Wd, device=dev).to(BF16)
+        d4 = d.double().view(B, nv, na, Wd)
+        gv, ga = kc.Guarded(B * nv, Wd, BF16, device=dev), kc.Guarded(B * na, Wd, BF16, device=dev)
+        ops.pair_reduce(d, B, nv, na, Wd, gv.t, ga.t)
+        wv, wa = d4.sum(2).reshape(-1, Wd), d4.sum(1).reshape(-1, Wd)
+        elem(ptag + ' pair_reduce v', 'fuzz_rows', gv.t, wv, kc.sum_bound(d4.abs().sum(2).reshape(-1, Wd), na, wv, BF16))
+        elem(ptag + ' pair_reduce a', 'fuzz_rows', ga.t, wa, kc.sum_bound(d4.abs().sum(1).reshape(-1, Wd), nv, wa, BF16))
+        guard(ptag + ' pair_reduce v', gv)
+        guard(ptag + ' pair_reduce a', ga)
+        # patch_gather
+        C, H, W = rng.choice([1, 3]), 16 * rng.randint(1, 8), 16 * rng.randint(1, 8)
+        Lp = (H // 16) * (W // 16)
+        nkp = rng.randint(1, Lp)
+        img = torch.randn(B, C, H, W, device=dev)
+        ids = torch.stack([torch.randperm(Lp, device=dev)[:nkp] for _ in range(B)]).to(torch.int32)
+        cols = img.reshape(B, C, H // 16, 16, W // 16, 16).permute(0, 2, 4, 1, 3, 5).reshape(B, Lp, C * 256)
+        g = kc.Guarded(B * nkp, C * 256, BF16, device=dev)
+        ops.patch_gather(img, ids, nkp, g.t)
+        same(f'patch_gather #{it} B{B} {C}x{H}x{W} keep {nkp}', g.t.view(B, nkp, -1),
+             cols.gather(1, ids.long().unsqueeze(-1).expand(-1, -1, C * 256)).to(BF16))
+        guard(f'patch_gather #{it}', g)
 
 
 def fuzz_ln_fused(rng, n):
@@ -386,6 +475,7 @@ if __name__ == '__main__':
     fuzz_ln(rng, nl)
     fuzz_ln_fused(rng, nl)
     fuzz_gang(rng, ngg)
+    fuzz_rows(rng, nl)
     print(f'fuzz seed {seed}: {len(FAILS)} failures')
     for f in FAILS[:20]:
         print('  ', f)

@@ -54,6 +54,25 @@ def kept(name, t, before, mask=None):
     print(f'{"PASS" if n == 0 else "FAIL"} {name} untouched: {n} elements changed' + (f' — first at {kc.tile_of(i, tuple(t.shape))}' if n else ''), flush=True)
 
 
+def same(name, got, ref):
+    """bit-exact: every element of ``got`` equals ``ref`` bit for bit (tests/kcheck.py exact)"""
+    n, msg = kc.exact(got, ref, name)
+    RESULTS.append((name + ' bit-exact', float(n), 0.0, n == 0))
+    print(f'{"PASS" if n == 0 else "FAIL"} {name} bit-exact: {n} elements differ' + (f' — {msg}' if msg else ''), flush=True)
+
+
+def rejected(name, fn):
+    """a call outside the header's contract must fail with an error (RuntimeError from the C ABI), not run"""
+    try:
+        fn()
+        torch.cuda.synchronize()
+        ok = False
+    except RuntimeError:
+        ok = True
+    RESULTS.append((name + ' rejected', 0.0 if ok else 1.0, 0.0, ok))
+    print(f'{"PASS" if ok else "FAIL"} {name} rejected by the C ABI' + ('' if ok else ' — it ran'), flush=True)
+
+
 def check(fn):
     def run():
         try:
@@ -508,6 +527,14 @@ def patch_gather3d():
         ops.patch_gather(x, ids, nk, A2, pt)
         ref = torch.gather(cols, 1, ids.long().unsqueeze(-1).expand(-1, -1, cols.shape[-1]))
         report(f'patch_gather3d kept {B}x{C}x{T}x{H}x{W}', rel(A2.view(B, nk, -1), ref.to(BF16)), 1e-6)
+        # bit-exact (a copy + one round-to-nearest-even), guarded, and the fp32 twin dav_patch_gather_f32 (an exact copy)
+        for sel, n, want in ((None, L, cols), (ids, nk, ref)):
+            for dt in (BF16, F32):
+                nm = f'patch_gather3d {"kept" if sel is not None else "all"} {B}x{C}x{T}x{H}x{W}' + (' fp32' if dt == F32 else '')
+                g = kc.Guarded(B * n, C * pt * 256, dt, device=dev)
+                ops.patch_gather(x, sel, n, g.t, pt)
+                same(nm, g.t.view(B, n, -1), want.to(dt))
+                guard(nm, g)
 
 
 @check
@@ -707,13 +734,21 @@ def dropout():
 def window_attention():
     """Swin decoder kernels (models/swin.py): attention with the relative-position bias + shift mask on the A x A corner of
     [A window tokens | nF fusion tokens] sequences (bias table per window, b % nb), its dS output and the table gradient
-    reduced from it, and the unfold / fold row movers — against plain torch."""
+    reduced from it, and the unfold / fold row movers — against plain torch, then elementwise (tests/kcheck.py): every output
+    starts poisoned (accumulated ones prefilled), the bf16 kernels and their fp32 twins are held to float64 bounds, the bias
+    build and the row copies are bit-exact."""
     LOG2E = 1.4426950408889634
-    for (B, nW, H, A, nF, d, masked) in [(2, 4, 2, 16, 9, 32, True), (3, 6, 2, 16, 9, 32, False), (2, 20, 16, 16, 32, 32, True),
-                                          (1, 1, 2, 16, 3, 32, False), (2, 4, 2, 16, 16, 64, True)]:
+    for (B, nW, H, A, nF, d, masked, pad) in [(2, 4, 2, 16, 9, 32, True, 0), (3, 6, 2, 16, 9, 32, False, 0), (2, 20, 16, 16, 32, 32, True, 0),
+                                               (1, 1, 2, 16, 3, 32, False, 0), (2, 4, 2, 16, 16, 64, True, 0),
+                                               # 7 x 7 windows (SwinTransformerBlock's default: N = 69 crosses a 64-key tile) and one
+                                               # 3 x 3 window (models/swin.py:60-62: a grid no larger than the window), bias_ld > Nk rounded up
+                                               (2, 4, 2, 49, 20, 32, True, 32), (3, 1, 2, 9, 5, 32, False, 32),
+                                               # the base_swin decoders (image 16 windows, audio 20) at the bench batch
+                                               (64, 16, 16, 16, 32, 32, True, 0), (64, 20, 16, 16, 32, 32, False, 0)]:
         N, D = A + nF, H * d
-        ld = (N + 31) // 32 * 32
-        win = int(A ** 0.5)
+        Nkp = (N + 31) // 32 * 32
+        ld = Nkp + pad
+        win = int(round(A ** 0.5))
         T = (2 * win - 1) ** 2
         table = rnd(T, H, seed=71, scale=0.7)
         coords = torch.stack(torch.meshgrid(torch.arange(win), torch.arange(win), indexing='ij')).flatten(1)
@@ -728,14 +763,23 @@ def window_attention():
         bias2 = kc.poisoned((nb, H, N, ld), F32, dev)
         ops.relpos_bias_build(table, index32, mask, nb, H, A, N, ld, LOG2E, bias2)
         full = torch.zeros(nb, H, N, N, device=dev)
-        full[:, :, :A, :A] = table[index.reshape(-1)].view(A, A, H).permute(2, 0, 1)[None] + (mask[:, None] if masked else 0.0)
+        corner = table[index.reshape(-1)].view(A, A, H).permute(2, 0, 1)[None] + (mask[:, None] if masked else 0.0)
+        full[:, :, :A, :A] = corner
         report(f'relpos_bias_build nW{nW} H{H} N{N}', rel(bias2[..., :N] / LOG2E, full) + (float(bias2[..., N:].abs().max()) if ld > N else 0.0), 1e-6)
+        # (table[index] + mask) * mul in fp32 on the corner, +0 everywhere else (padding columns included)
+        bias_n = kc.poisoned((nb, H, N, ld), F32, dev)                  # natural units: the fp32 twins' bias
+        ops.relpos_bias_build(table, index32, mask, nb, H, A, N, ld, 1.0, bias_n)
+        for mul, got in ((LOG2E, bias2), (1.0, bias_n)):
+            want = torch.zeros(nb, H, N, ld, device=dev)
+            want[:, :, :A, :A] = corner * mul
+            same(f'relpos_bias_build nW{nW} H{H} A{A} N{N} ld{ld} mul{mul:.3f}', got, want)
         buf = rnd(B * nW, N, 3, H, d, dtype=BF16, seed=73)
         q = buf[:, :, 0].permute(0, 2, 1, 3).float().requires_grad_(True)
         k = buf[:, :, 1].permute(0, 2, 1, 3).float().requires_grad_(True)
         v = buf[:, :, 2].permute(0, 2, 1, 3).float().requires_grad_(True)
         scale = d ** -0.5
-        logits = (q @ k.transpose(-2, -1)) * scale + full.repeat(B * nW // nb, 1, 1, 1)
+        fullrep = full.repeat(B * nW // nb, 1, 1, 1)
+        logits = (q @ k.transpose(-2, -1)) * scale + fullrep
         logits.retain_grad()
         ref = logits.softmax(-1) @ v
         O = kc.poisoned((B * nW * N, D), BF16, dev)
@@ -743,43 +787,119 @@ def window_attention():
         st = (N * 3 * D, 3 * D) * 3
         p0 = buf.data_ptr()
         ops.attn_bias_fwd(p0, p0 + 2 * D, p0 + 4 * D, O, LSE, B * nW, H, N, N, d, d, *st, N * D, D, scale, bias2, nb, ld)
-        tag = f'window attn B{B} nW{nW} H{H} N{N} d{d} mask{int(masked)}'
+        tag = f'window attn B{B} nW{nW} H{H} A{A} N{N} d{d} mask{int(masked)}'
         report(tag + ' fwd', rel(O.view(B * nW, N, H, d).permute(0, 2, 1, 3), ref), 1e-2)
         report(tag + ' lse', rel(LSE, torch.logsumexp(logits, -1)), 1e-4)
         dO = rnd(B * nW * N, D, dtype=BF16, seed=74)
-        ref.backward(dO.view(B * nW, N, H, d).permute(0, 2, 1, 3).float())
-        dbuf = torch.zeros_like(buf)
-        dS = torch.zeros(B * nW, H, N, ld, device=dev)
+        dOv = dO.view(B * nW, N, H, d).permute(0, 2, 1, 3)
+        ref.backward(dOv.float())
+        Ok = O.view(B * nW, N, H, d).permute(0, 2, 1, 3)
+        r64 = kc.attn_bounds(q, k, v, dOv, Ok, scale, bias=fullrep)
+        elem(tag + ' fwd', 'window_attention', Ok, r64['O'], r64['bO'])
+        elem(tag + ' lse', 'window_attention', LSE, r64['lse'], r64['blse'])
+        dbuf = kc.poisoned(buf.shape, BF16, dev)
+        dS = kc.poisoned((B * nW, H, N, ld), F32, dev)
+        Delta = kc.poisoned(LSE.shape, F32, dev)
         d0 = dbuf.data_ptr()
-        ops.attn_bias_bwd(p0, p0 + 2 * D, p0 + 4 * D, O, dO, LSE, torch.empty_like(LSE), d0, d0 + 2 * D, d0 + 4 * D, B * nW, H, N, N, d, d,
+        ops.attn_bias_bwd(p0, p0 + 2 * D, p0 + 4 * D, O, dO, LSE, Delta, d0, d0 + 2 * D, d0 + 4 * D, B * nW, H, N, N, d, d,
                           *st, N * D, D, N * D, D, *st, scale, bias2, nb, ld, dS)
         report(tag + ' dq', rel(dbuf[:, :, 0].permute(0, 2, 1, 3), q.grad), 2e-2)
         report(tag + ' dk', rel(dbuf[:, :, 1].permute(0, 2, 1, 3), k.grad), 2e-2)
         report(tag + ' dv', rel(dbuf[:, :, 2].permute(0, 2, 1, 3), v.grad), 2e-2)
         report(tag + ' dS', rel(dS[..., :N], logits.grad), 2e-2)
-        dtab = torch.zeros(T, H, device=dev)
-        ops.relpos_bias_bwd(dS, index32, B * nW, H, A, N, ld, T, dtab)
+        for i, g in enumerate(('dq', 'dk', 'dv')):
+            elem(f'{tag} {g}', 'window_attention', dbuf[:, :, i].permute(0, 2, 1, 3), r64[g], r64['b' + g])
+        elem(tag + ' dS', 'window_attention', dS[..., :N], r64['dS'], r64['bdS'])
+        dO64, Ok64 = dOv.double(), Ok.double()
+        delta64 = (dO64 * Ok64).sum(-1)                                  # Delta = dO . O (the kernel's bf16 O): a d-term fp32 sum
+        elem(tag + ' Delta', 'window_attention', Delta, delta64, kc.sum_bound((dO64 * Ok64).abs().sum(-1), d, delta64))
+        # header contract: dS columns [Nk, Nk rounded up to 32) receive finite values, the columns beyond keep their bits
+        nfin = int((~torch.isfinite(dS[..., N:Nkp])).sum())
+        report(tag + f' dS columns {N}..{Nkp} finite', float(nfin), 0.0)
+        kept(tag + f' dS columns {Nkp}..{ld}', dS[..., Nkp:], kc.poisoned(dS[..., Nkp:].shape, F32, dev))
         want = torch.zeros(T, H, device=dev)
         want.index_add_(0, index.reshape(-1), dS[:, :, :A, :A].sum(0).permute(1, 2, 0).reshape(A * A, H))
-        report(tag + ' dtable (from the kernel dS)', rel(dtab, want), 1e-5)
+        if A * A <= 1024:
+            gz = kc.Guarded(T, H, F32, device=dev, fill='zero')
+            ops.relpos_bias_bwd(dS, index32, B * nW, H, A, N, ld, T, gz.t)
+            report(tag + ' dtable (from the kernel dS)', rel(gz.t, want), 1e-5)
+            guard(tag + ' dtable', gz)
+            # dtable += ...: into a random prefill; entry e sums B * nW * (pairs of e) terms + the prefill
+            pre = kc.prefilled((T, H), F32, dev, seed=78)
+            dtab = pre.clone()
+            ops.relpos_bias_bwd(dS, index32, B * nW, H, A, N, ld, T, dtab)
+            cS = dS[:, :, :A, :A].double()
+            want64 = pre.double().index_add(0, index.reshape(-1), cS.sum(0).permute(1, 2, 0).reshape(A * A, H))
+            absum = pre.double().abs().index_add(0, index.reshape(-1), cS.abs().sum(0).permute(1, 2, 0).reshape(A * A, H))
+            npairs = torch.bincount(index.reshape(-1), minlength=T).double()[:, None]
+            elem(tag + ' dtable += (prefilled)', 'relpos_bias_bwd', dtab, want64, kc.sum_bound(absum, B * nW * npairs + 1, want64))
+        else:                   # header: A * A <= 1024
+            rejected(f'relpos_bias_bwd A{A}', lambda: ops.relpos_bias_bwd(dS, index32, B * nW, H, A, N, ld, T, kc.prefilled((T, H), F32, dev)))
+        # ---- the fp32 twins (dav_attn_bias_fwd_f32 / _bwd_f32): fp32 operands of the same values, natural-units bias
+        b32 = buf.float()
+        p1 = b32.data_ptr()
+        O32, LSE32 = kc.poisoned((B * nW * N, D), F32, dev), kc.poisoned((B * nW, H, N), F32, dev)
+        ops.attn_bias_fwd(p1, p1 + 4 * D, p1 + 8 * D, O32, LSE32, B * nW, H, N, N, d, d, *st, N * D, D, scale, bias_n, nb, ld)
+        O32v = O32.view(B * nW, N, H, d).permute(0, 2, 1, 3)
+        dO32 = dO.float()
+        up = kc.f32_attn_up(q, k, scale, fullrep)
+        r32 = kc.attn_bounds(q, k, v, dOv, O32v, scale, up=up, r_out=kc.out_round(F32), bias=fullrep)
+        tag32 = tag + ' fp32'
+        elem(tag32 + ' fwd', 'window_attention_f32', O32v, r32['O'], r32['bO'])
+        elem(tag32 + ' lse', 'window_attention_f32', LSE32, r32['lse'], r32['blse'])
+        dbuf32 = kc.poisoned(b32.shape, F32, dev)
+        dS32 = kc.poisoned((B * nW, H, N, ld), F32, dev)
+        d1 = dbuf32.data_ptr()
+        ops.attn_bias_bwd(p1, p1 + 4 * D, p1 + 8 * D, O32, dO32, LSE32, kc.poisoned(LSE.shape, F32, dev), d1, d1 + 4 * D, d1 + 8 * D,
+                          B * nW, H, N, N, d, d, *st, N * D, D, N * D, D, *st, scale, bias_n, nb, ld, dS32)
+        for i, g in enumerate(('dq', 'dk', 'dv')):
+            elem(f'{tag32} {g}', 'window_attention_f32', dbuf32[:, :, i].permute(0, 2, 1, 3), r32[g], r32['b' + g])
+        elem(tag32 + ' dS', 'window_attention_f32', dS32[..., :N], r32['dS'], r32['bdS'])
+        kept(tag32 + f' dS columns {N}..{ld}', dS32[..., N:], kc.poisoned(dS32[..., N:].shape, F32, dev))
+        del r64, r32, fullrep, logits, ref
         # ---- row movers: [B, nF + L, C] <-> [B * nW, A + nF, C] through a random token permutation
         L, C = nW * A, 96
         rows = torch.randperm(L, generator=torch.Generator().manual_seed(5)).to(dev)
         inv = torch.empty_like(rows); inv[rows] = torch.arange(L, device=dev)
+        rows32, inv32 = rows.to(torch.int32), inv.to(torch.int32)
         x = rnd(B, nF + L, C, seed=75)
         seq = kc.poisoned((B * nW * N, C), BF16, dev)
-        ops.window_unfold(x, rows.to(torch.int32), B, nW, A, nF, L, C, 0.5, seq)
+        ops.window_unfold(x, rows32, B, nW, A, nF, L, C, 0.5, seq)
         want = torch.cat([x[:, nF:][:, rows].reshape(B * nW, A, C), (0.5 * x[:, None, :nF]).expand(B, nW, nF, C).reshape(B * nW, nF, C)], 1)
         report(f'window_unfold nW{nW} nF{nF}', rel(seq.view(B * nW, N, C), want), 4e-3)
+        fs = 1.0 / nW
+        for sdt, odt in ((F32, BF16), (BF16, BF16), (F32, F32), (BF16, F32)):
+            src = x.to(sdt)
+            name = f'window_unfold nW{nW} A{A} nF{nF} {str(sdt)[6:]}->{str(odt)[6:]}'
+            g = kc.Guarded(B * nW * N, C, odt, device=dev)
+            if sdt == BF16 and odt == F32:           # header: bf16 -> fp32 is not provided
+                rejected(name, lambda: ops.window_unfold(src, rows32, B, nW, A, nF, L, C, fs, g.t))
+                continue
+            ops.window_unfold(src, rows32, B, nW, A, nF, L, C, fs, g.t)
+            o4 = g.t.view(B, nW, N, C)
+            same(name + ' token rows', o4[:, :, :A], src[:, nF:][:, rows].reshape(B, nW, A, C).to(odt))
+            same(name + ' fusion rows', o4[:, :, A:], (fs * src[:, None, :nF].float()).expand(B, nW, nF, C).to(odt))
+            guard(name, g)
         t = rnd(B * nW * N, C, seed=76)
         res = rnd(B, nF + L, C, seed=77)
         out = kc.poisoned((B, nF + L, C), F32, dev)
-        ops.window_fold(t, inv.to(torch.int32), res, B, nW, A, nF, L, C, 1.0 / nW, out)
+        ops.window_fold(t, inv32, res, B, nW, A, nF, L, C, 1.0 / nW, out)
         tv = t.view(B, nW, N, C)
-        tok = torch.empty(B, L, C, device=dev)
-        tok[:, rows] = tv[:, :, :A].reshape(B, L, C)
+        tok = tv[:, :, :A].reshape(B, L, C)[:, inv]
         want = res + torch.cat([tv[:, :, A:].mean(1), tok], 1)
         report(f'window_fold nW{nW} nF{nF}', rel(out, want), 1e-6)
+        # token rows: one fp32 add (none without res); fusion rows: res + fs * (sum over the nW windows)
+        for with_res in (True, False):
+            name = f'window_fold nW{nW} A{A} nF{nF} res{int(with_res)}'
+            g = kc.Guarded(B * (nF + L), C, F32, device=dev)
+            ops.window_fold(t, inv32, res if with_res else None, B, nW, A, nF, L, C, fs, g.t)
+            o3 = g.t.view(B, nF + L, C)
+            same(name + ' token rows', o3[:, nF:], res[:, nF:] + tok if with_res else tok)
+            r0 = res[:, :nF].double() if with_res else torch.zeros(B, nF, C, dtype=torch.float64, device=dev)
+            f64 = r0 + fs * tv[:, :, A:].double().sum(1)
+            absum = r0.abs() + fs * tv[:, :, A:].double().abs().sum(1)
+            elem(name + ' fusion rows', 'window_fold', o3[:, :nF], f64, kc.sum_bound(absum, nW + 2, f64))
+            guard(name, g)
 
 
 @check
@@ -1027,76 +1147,168 @@ def masking():
     report('mask_build vs torch.argsort 64x320', 0.0 if ok else 1.0, 0.0)
 
 
+def base_shapes():
+    """The bench workload's shapes (config 'base' at bench.py's batch of 64 pairs): per modality (C, H, W, patches, kept), the
+    decoder width, the fusion rows and the factorised (v, a) pairs (nv, na, pair widths: key Da and value D)."""
+    from deepavfusion_amd.configs import CONFIGS
+    c = CONFIGS['base']
+    mods = []
+    for C, (H, W), ratio in ((3, c.image_size, c.image_mask_ratio), (1, c.audio_size, c.audio_mask_ratio)):
+        L = (H // c.patch) * (W // c.patch)
+        mods.append((C, H, W, L, int(L * (1 - ratio))))          # len_keep of models/avmae.py:132
+    return dict(B=64, mods=mods, D=c.decoder_dim, nF=sum(c.fusion_tkns), nv=c.fusion_tkns[1], na=c.fusion_tkns[2],
+                widths=(int(c.embed_dim * c.fusion_attn_ratio), c.embed_dim))
+
+
+def _row_movers(B, C, H, W, nk, D, nF, tag, seed):
+    """patch_gather (+ its fp32 twin), unshuffle_fwd, rows_gather_cast (+ fp32 twin), unshuffle_bwd_reduce at one shape: copies and
+    single roundings bit-exact, every output guarded, the accumulated ones prefilled"""
+    L = (H // 16) * (W // 16)
+    gen = torch.Generator().manual_seed(seed)
+    img = rnd(B, C, H, W, seed=seed)
+    ids = torch.stack([torch.randperm(L, generator=gen)[:nk] for _ in range(B)]).to(dev).to(torch.int32)
+    cols = img.reshape(B, C, H // 16, 16, W // 16, 16).permute(0, 2, 4, 1, 3, 5).reshape(B, L, C * 256)
+    kept_cols = cols.gather(1, ids.long().unsqueeze(-1).expand(-1, -1, C * 256)).reshape(B * nk, -1)
+    for sel, n, want in ((ids, nk, kept_cols), (None, L, cols.reshape(B * L, -1))):
+        name = f'patch_gather {"kept" if sel is not None else "all"} {tag}'
+        for dt in (BF16, F32):
+            g = kc.Guarded(B * n, C * 256, dt, device=dev)
+            ops.patch_gather(img, sel, n, g.t)
+            nm = name + (' fp32' if dt == F32 else '')
+            if dt == BF16:
+                report(nm, rel(g.t, want), 4e-3)
+            same(nm, g.t, want.to(dt))
+            guard(nm, g)
+    # un-shuffle: out[b, nF + r] = (kept ? emb : mask_token) + pos[r] — one fp32 add; the nF leading rows are not the kernel's
+    emb, mt, pos = rnd(B * nk, D, seed=seed + 1), rnd(D, seed=seed + 2), rnd(L, D, seed=seed + 3)
+    restore = torch.stack([torch.randperm(L, generator=gen) for _ in range(B)]).to(dev)
+    r32 = restore.to(torch.int32)
+    g = kc.Guarded(B * (nF + L), D, F32, device=dev)
+    before = g.t.clone()
+    out = g.t.view(B, nF + L, D)
+    ops.unshuffle_fwd(emb, mt, pos, r32, B, L, nk, D, out, (nF + L) * D, nF)
+    full = torch.cat([emb.view(B, nk, D), mt.view(1, 1, D).expand(B, L - nk, D)], 1)
+    want = full.gather(1, restore.unsqueeze(-1).expand(-1, -1, D)) + pos
+    report(f'unshuffle_fwd {tag}', rel(out[:, nF:], want), 1e-6)
+    same(f'unshuffle_fwd {tag}', out[:, nF:], want)
+    lead = torch.zeros(B, nF + L, dtype=torch.bool, device=dev)
+    lead[:, :nF] = True
+    kept(f'unshuffle_fwd {tag} the {nF} leading rows', g.t, before, lead.view(-1))
+    guard(f'unshuffle_fwd {tag}', g)
+    gx = rnd(B, nF + L, D, seed=seed + 4)
+    keep = torch.argsort(restore, dim=1)[:, :nk].to(torch.int32)
+    for sel, n, want in ((keep, nk, gx[:, nF:].gather(1, keep.long().unsqueeze(-1).expand(-1, -1, D))), (None, L, gx[:, nF:])):
+        name = f'rows_gather_cast {"ids" if sel is not None else "row_off"} {tag}'
+        for dt in (BF16, F32):
+            g = kc.Guarded(B * n, D, dt, device=dev)
+            ops.rows_gather_cast(gx, (nF + L) * D, nF, sel, B, n, D, g.t)
+            nm = name + (' fp32' if dt == F32 else '')
+            if dt == BF16:
+                report(nm, rel(g.t.view(B, n, D), want), 4e-3)
+            same(nm, g.t.view(B, n, D), want.to(dt))
+            guard(nm, g)
+    # dpos += sum over b (B terms), dmask_token += sum over the masked (b, r) (B L terms, atomics) — into zeros, then random prefills
+    gp, gm = kc.Guarded(L, D, F32, device=dev, fill='zero'), kc.Guarded(1, D, F32, device=dev, fill='zero')
+    ops.unshuffle_bwd_reduce(gx, (nF + L) * D, nF, r32, B, L, nk, D, gp.t, gm.t)
+    msk = (restore >= nk).float().unsqueeze(-1)
+    report(f'unshuffle dpos {tag}', rel(gp.t, gx[:, nF:].sum(0)), 1e-5)
+    report(f'unshuffle dmask_token {tag}', rel(gm.t[0], (gx[:, nF:] * msk).sum((0, 1))), 1e-5)
+    pp, pm = kc.prefilled((L, D), F32, dev, seed=seed + 5), kc.prefilled((1, D), F32, dev, seed=seed + 6)
+    gp.set(pp)
+    gm.set(pm)
+    ops.unshuffle_bwd_reduce(gx, (nF + L) * D, nF, r32, B, L, nk, D, gp.t, gm.t)
+    g64, m64 = gx[:, nF:].double(), msk.double()
+    wp = pp.double() + g64.sum(0)
+    elem(f'unshuffle dpos += (prefilled) {tag}', 'unshuffle_bwd', gp.t, wp, kc.sum_bound(pp.double().abs() + g64.abs().sum(0), B + 1, wp))
+    wm = pm.double() + (g64 * m64).sum((0, 1))
+    elem(f'unshuffle dmask_token += (prefilled) {tag}', 'unshuffle_bwd', gm.t, wm,
+         kc.sum_bound(pm.double().abs() + (g64 * m64).abs().sum((0, 1)), B * L + 1, wm))
+    guard(f'unshuffle dpos {tag}', gp)
+    guard(f'unshuffle dmask_token {tag}', gm)
+
+
+def _patch_loss(B, C, H, W, tag, seed, edges=False):
+    """dav_patch_mse_fwd / _bwd / _bwd_f32 against the oracle (rel, as before) and elementwise against kcheck.mse_bounds.
+    edges: a constant patch (variance 0: rstd = 1 / sqrt(1e-6)), a row with mask 0 and a batch element with every patch masked."""
+    from oracle import avmae_oracle as O
+    L, P = (H // 16) * (W // 16), 256 * C
+    im = rnd(B, C, H, W, seed=seed)
+    pred = rnd(B, L, P, seed=seed + 1)
+    mask = (torch.rand(B, L, generator=torch.Generator().manual_seed(seed)) > 0.3).float().to(dev)
+    if edges:
+        im[0, :, :16, :16] = 0.3
+        mask[0, 0], mask[0, 1], mask[B - 1] = 1.0, 0.0, 1.0
+    gsc = torch.tensor(0.7, device=dev)
+    for norm in (True, False):
+        t = f'{tag} norm{int(norm)}'
+        pr = pred.clone().requires_grad_(True)
+        ref = O.forward_loss(O.patchify(im, (16, 16)), pr, mask, norm)
+        (ref * gsc).backward()
+        lp, tm, tr = (kc.poisoned((B * L,), F32, dev) for _ in range(3))
+        loss, ms = kc.poisoned((1,), F32, dev), kc.poisoned((1,), F32, dev)
+        ops.patch_mse_fwd(im, pred, mask, norm, lp, tm, tr, loss, ms)
+        report(f'patch_mse fwd {t}', abs(float(loss) - float(ref)) / abs(float(ref)), 1e-5)
+        M = kc.mse_bounds(im, pred, mask, norm)
+        for nm, got in (('loss_patch', lp), ('tmean', tm), ('trstd', tr)):
+            elem(f'patch_mse {nm} {t}', 'patch_mse', got.view(B, L), M[nm], M['b' + nm])
+        elem(f'patch_mse loss {t}', 'patch_mse', loss[0], M['loss'], M['bloss'])
+        same(f'patch_mse mask_sum {t}', ms, mask.sum().view(1))
+        for dt in (BF16, F32):
+            nm = f'patch_mse bwd {t}' + (' fp32' if dt == F32 else '')
+            g = kc.Guarded(B * L, P, dt, device=dev)
+            ops.patch_mse_bwd(im, pred, mask, tm, tr, ms, gsc, g.t)
+            if dt == BF16:
+                report(nm, rel(g.t.view(B, L, P), pr.grad), 5e-3)
+            want, bnd = kc.mse_grad(im, pred, mask, tm, tr, ms, gsc, dt)
+            elem(nm, 'patch_mse', g.t.view(B, L, P), want, bnd)          # masked-out rows: bound 0, exactly 0
+            guard(nm, g)
+
+
+def _pairs(B, nv, na, Wd, tag, seed):
+    """pair_expand (one fp32 add + a rounding: bit-exact) and pair_reduce (na- / nv-term sums), bf16 kernels and fp32 twins"""
+    Pv, Pa = rnd(B * nv, Wd, seed=seed), rnd(B * na, Wd, seed=seed + 1)
+    ref = (Pv.view(B, nv, 1, Wd) + Pa.view(B, 1, na, Wd)).reshape(-1, Wd)
+    for dt in (BF16, F32):
+        nm = f'pair_expand {tag}' + (' fp32' if dt == F32 else '')
+        g = kc.Guarded(B * nv * na, Wd, dt, device=dev)
+        ops.pair_expand(Pv, Pa, B, nv, na, Wd, g.t)
+        if dt == BF16:
+            report(nm, rel(g.t, ref), 4e-3)
+        same(nm, g.t, ref.to(dt))
+        guard(nm, g)
+    d = rnd(B * nv * na, Wd, dtype=BF16, seed=seed + 2)
+    d4 = d.double().view(B, nv, na, Wd)
+    wv, wa = d4.sum(2).reshape(-1, Wd), d4.sum(1).reshape(-1, Wd)
+    for dt in (BF16, F32):
+        nm = f'pair_reduce {tag}' + (' fp32' if dt == F32 else '')
+        gv, ga = kc.Guarded(B * nv, Wd, dt, device=dev), kc.Guarded(B * na, Wd, dt, device=dev)
+        ops.pair_reduce(d.to(dt), B, nv, na, Wd, gv.t, ga.t)
+        if dt == BF16:
+            report(nm + ' v', rel(gv.t, wv), 4e-3)
+            report(nm + ' a', rel(ga.t, wa), 4e-3)
+        elem(nm + ' v', 'pair_reduce', gv.t, wv, kc.sum_bound(d4.abs().sum(2).reshape(-1, Wd), na, wv, dt))
+        elem(nm + ' a', 'pair_reduce', ga.t, wa, kc.sum_bound(d4.abs().sum(1).reshape(-1, Wd), nv, wa, dt))
+        guard(nm + ' v', gv)
+        guard(nm + ' a', ga)
+
+
 @check
 def misc_kernels():
-    from oracle import avmae_oracle as O
-    B, C, H, W, nk = 3, 3, 64, 96, 5
-    img = rnd(B, C, H, W, seed=41)
-    L = (H // 16) * (W // 16)
-    ids = torch.stack([torch.randperm(L)[:nk] for _ in range(B)]).to(dev).to(torch.int32)
-    A = kc.poisoned((B * nk, C * 256), BF16, dev)
-    ops.patch_gather(img, ids, nk, A)
-    cols = img.reshape(B, C, H // 16, 16, W // 16, 16).permute(0, 2, 4, 1, 3, 5).reshape(B, L, C * 256)
-    ref = cols.gather(1, ids.long().unsqueeze(-1).expand(-1, -1, C * 256)).reshape(B * nk, -1)
-    report('patch_gather', rel(A, ref), 4e-3)
-    A2 = kc.poisoned((B * L, C * 256), BF16, dev)
-    ops.patch_gather(img, None, L, A2)
-    report('patch_gather all', rel(A2, cols.reshape(B * L, -1)), 4e-3)
-    # unshuffle
-    D, nF = 64, 3
-    emb, mt, pos = rnd(B * nk, D, seed=42), rnd(D, seed=43), rnd(L, D, seed=44)
-    restore = torch.stack([torch.randperm(L) for _ in range(B)]).to(dev)
-    out = torch.zeros(B, nF + L, D, device=dev)
-    ops.unshuffle_fwd(emb, mt, pos, restore.to(torch.int32), B, L, nk, D, out, (nF + L) * D, nF)
-    full = torch.cat([emb.view(B, nk, D), mt.view(1, 1, D).expand(B, L - nk, D)], 1)
-    ref = full.gather(1, restore.unsqueeze(-1).expand(-1, -1, D)) + pos
-    report('unshuffle_fwd', rel(out[:, nF:], ref), 1e-6)
-    gx = rnd(B, nF + L, D, seed=45)
-    keep = torch.argsort(restore, dim=1)[:, :nk].to(torch.int32)
-    o = kc.poisoned((B * nk, D), BF16, dev)
-    ops.rows_gather_cast(gx, (nF + L) * D, nF, keep, B, nk, D, o)
-    report('rows_gather_cast', rel(o.view(B, nk, D), gx[:, nF:].gather(1, keep.long().unsqueeze(-1).expand(-1, -1, D))), 4e-3)
-    dpos, dmt = torch.zeros(L, D, device=dev), torch.zeros(D, device=dev)
-    ops.unshuffle_bwd_reduce(gx, (nF + L) * D, nF, restore.to(torch.int32), B, L, nk, D, dpos, dmt)
-    report('unshuffle dpos', rel(dpos, gx[:, nF:].sum(0)), 1e-5)
-    msk = (restore >= nk).float().unsqueeze(-1)
-    report('unshuffle dmask_token', rel(dmt, (gx[:, nF:] * msk).sum((0, 1))), 1e-5)
-    # loss
-    for Cc in (3, 1):
-        im = rnd(B, Cc, H, W, seed=46)
-        P = 256 * Cc
-        pred = rnd(B, L, P, seed=47).requires_grad_(True)
-        mask = (torch.rand(B, L, device=dev) > 0.3).float()
-        for norm in (True, False):
-            tgt = O.patchify(im, (16, 16))
-            ref = O.forward_loss(tgt, pred, mask, norm)
-            gsc = torch.tensor(0.7, device=dev)
-            pred.grad = None
-            (ref * gsc).backward()
-            lp, tm, tr = kc.poisoned((B * L,), F32, dev), torch.empty(B * L, device=dev), torch.empty(B * L, device=dev)      # (tm / tr: norm-pix statistics only)
-            loss, ms = kc.poisoned((1,), F32, dev), kc.poisoned((1,), F32, dev)
-            ops.patch_mse_fwd(im, pred.detach(), mask, norm, lp, tm, tr, loss, ms)
-            report(f'patch_mse fwd C{Cc} norm{int(norm)}', abs(float(loss) - float(ref)) / abs(float(ref)), 1e-5)
-            dp = kc.poisoned((B * L, P), BF16, dev)
-            ops.patch_mse_bwd(im, pred.detach(), mask, tm, tr, ms, gsc, dp)
-            report(f'patch_mse bwd C{Cc} norm{int(norm)}', rel(dp.view(B, L, P), pred.grad), 5e-3)
-    # pairs
-    nv, na, Wd = 3, 2, 64
-    Pv, Pa = rnd(B * nv, Wd, seed=48), rnd(B * na, Wd, seed=49)
-    out = kc.poisoned((B * nv * na, Wd), BF16, dev)
-    ops.pair_expand(Pv, Pa, B, nv, na, Wd, out)
-    ref = (Pv.view(B, nv, 1, Wd) + Pa.view(B, 1, na, Wd)).reshape(-1, Wd)
-    report('pair_expand', rel(out, ref), 4e-3)
-    d = rnd(B * nv * na, Wd, dtype=BF16, seed=50)
-    dPv, dPa = kc.poisoned((B * nv, Wd), BF16, dev), kc.poisoned((B * na, Wd), BF16, dev)
-    ops.pair_reduce(d, B, nv, na, Wd, dPv, dPa)
-    d4 = d.float().view(B, nv, na, Wd)
-    report('pair_reduce v', rel(dPv, d4.sum(2).reshape(-1, Wd)), 4e-3)
-    report('pair_reduce a', rel(dPa, d4.sum(1).reshape(-1, Wd)), 4e-3)
+    # row movers, loss and pairs: a toy shape, then the bench workload's
+    _row_movers(3, 3, 64, 96, 5, 64, 3, 'B3 3x64x96', seed=41)
+    for C in (3, 1):
+        _patch_loss(3, C, 64, 96, f'C{C} B3 64x96', seed=46)
+    _pairs(3, 3, 2, 64, 'B3 3x2x64', seed=48)
+    S = base_shapes()
+    for (C, H, W, L, nk) in S['mods']:
+        _row_movers(S['B'], C, H, W, nk, S['D'], S['nF'], f'B{S["B"]} {C}x{H}x{W} keep {nk}/{L}', seed=141)
+        _patch_loss(S['B'], C, H, W, f'C{C} B{S["B"]} {H}x{W}', seed=146, edges=True)
+    for Wd in S['widths']:
+        _pairs(S['B'], S['nv'], S['na'], Wd, f'B{S["B"]} {S["nv"]}x{S["na"]}x{Wd}', seed=148)
     # DropPath row kernels
     Bq, rq, Dq = 5, 7, 192
     res, yb, sc = rnd(Bq * rq, Dq, seed=61), rnd(Bq * rq, Dq, seed=62), torch.tensor([0., 1.25, 1.25, 0., 1.25], device=dev)
-    outp = torch.empty_like(res)
+    outp = kc.poisoned(res.shape, F32, dev)
     ops.rows_axpy(res, yb, sc, Bq, rq, Dq, outp)
     refp = res + yb * sc.repeat_interleave(rq)[:, None]
     report('rows_axpy', rel(outp, refp), 1e-6)
@@ -1147,7 +1359,7 @@ def misc_kernels():
         opt.step()
         bc = torch.tensor([1 - 0.9 ** step, math.sqrt(1 - 0.95 ** step)], device=dev)
         gcur = (g0 * step).clone()
-        ssq = torch.zeros(1, device=dev)
+        ssq = kc.poisoned((1,), F32, dev)                      # zeroed by the kernel first (header)
         keep = torch.tensor([0, 1 if step == 2 else 0], device=dev, dtype=torch.uint8)      # step 2: the second segment's gradient is kept
         ops.adamw_flat(p, gcur, m, v, pb, seg, hyper, 2, 0.9, 0.95, 1e-8, bc, sumsq_out=ssq, zero_grad=True, keep_grad=keep)
         report(f'adamw fused sumsq step{step}', abs(float(ssq) - float((g0 * step).double().pow(2).sum())) / float((g0 * step).double().pow(2).sum()), 1e-5)
@@ -1162,18 +1374,19 @@ def misc_kernels():
     one, nan, inf = torch.tensor([2.5], device=dev), torch.tensor([float('nan')], device=dev), torch.tensor([float('inf')], device=dev)
     gn, ws = kc.poisoned((1,), F32, dev), torch.empty(1024, device=dev)
     ops.l2norm(g0, gn, ws, 1.0)
-    sc, bad = kc.poisoned((1,), F32, dev), torch.zeros(1, device=dev, dtype=torch.int32)
+    BAD0 = 7                                                                           # bad_count is incremented: a prefilled counter
+    sc, bad = kc.poisoned((1,), F32, dev), torch.full((1,), BAD0, device=dev, dtype=torch.int32)
     clip = 0.25 * float(gn)
     ops.step_guard(one, one, gn, clip, 1.0, sc, bad)
     report('step_guard clip factor', abs(float(sc) - clip / (float(gn) + 1e-6)), 1e-7)
     ops.step_guard(one, None, gn, 10.0 * float(gn), 1.0, sc, bad)
     report('step_guard no clipping below the limit', abs(float(sc) - 1.0), 0.0)
     ops.step_guard(one, one, None, 0.0, 1.0, sc, bad)
-    report('step_guard plain', abs(float(sc) - 1.0) + float(bad), 0.0)
+    report('step_guard plain', abs(float(sc) - 1.0) + abs(int(bad) - BAD0), 0.0)
     for tag, (la, lb, nrm) in dict(nan_loss=(nan, one, None), inf_loss=(one, inf, gn), nan_norm=(one, one, nan)).items():
-        bad.zero_()
+        bad.fill_(BAD0)
         ops.step_guard(la, lb, nrm, 1.0, 1.0, sc, bad)
-        report(f'step_guard {tag} -> 0', abs(float(sc)) + abs(int(bad) - 1), 0.0)
+        report(f'step_guard {tag} -> 0', abs(float(sc)) + abs(int(bad) - BAD0 - 1), 0.0)
     ops.step_guard(one, one, gn, clip, 1.0, sc, bad)
     pa, ma, va, pba, ga = p.clone(), m.clone(), v.clone(), pb.clone(), g0.clone()
     pc, mc, vc, pbc, gc = p.clone(), m.clone(), v.clone(), pb.clone(), g0.clone()
@@ -1181,7 +1394,7 @@ def misc_kernels():
     ops.adamw_flat(pc, gc, mc, vc, pbc, seg, hyper, 2, 0.9, 0.95, 1e-8, bc, gscale_dev=sc)
     report('adamw gscale_dev == grad_scale (bit-equal)', float((pa != pc).sum() + (ma != mc).sum() + (va != vc).sum()), 0.0)
     sc.zero_()
-    pz, mz, vz, pbz, gz, ssq = p.clone(), m.clone(), v.clone(), pb.clone(), g0.clone(), torch.zeros(1, device=dev)
+    pz, mz, vz, pbz, gz, ssq = p.clone(), m.clone(), v.clone(), pb.clone(), g0.clone(), kc.poisoned((1,), F32, dev)
     ops.adamw_flat(pz, gz, mz, vz, pbz, seg, hyper, 2, 0.9, 0.95, 1e-8, bc, sumsq_out=ssq, zero_grad=True, gscale_dev=sc)
     report('adamw skipped step: p, m, v, mirror untouched', float((pz != p).sum() + (mz != m).sum() + (vz != v).sum() + (pbz != pb).sum()), 0.0)
     report('adamw skipped step: gradients zero-filled, sumsq reported', float(gz.abs().max()) + abs(float(ssq) / float(g0.double().pow(2).sum()) - 1.0), 1e-5)

@@ -19,6 +19,7 @@ GUARD_BYTES = 256                 # each guard band (a multiple of 16: the view 
 GUARD_BYTE = 0xA5                 # fill pattern of every byte outside the view (fp32 0xA5A5A5A5 / bf16 0xA5A5: finite, never a result)
 INT_POISON = -0x5A5A5A5B          # sentinel of int outputs
 U32 = 2.0 ** -24                  # unit roundoff of fp32
+FLT_MIN = 2.0 ** -126             # smallest normal fp32: the kernels flush what falls below it to 0
 U16 = 2.0 ** -8                   # unit roundoff of bf16 (8 significant bits): EXACTLY the worst case of one rounding, no slack —
                                   # the bf16-output bounds hold because the accumulation term adds to it; never lower this
 
@@ -144,6 +145,17 @@ def within(got, ref, bound, tag=''):
     return False, worst, msg
 
 
+def exact(got, ref, tag=''):
+    """Bit-for-bit equality of ``got`` with ``ref`` (same dtype and shape: a copy, a single rounding of the same fp32 value, +0
+    where +0 is due — a NaN poison or a -0 counts as a difference).  Returns (number of elements that differ, message naming the
+    first one and its 128- and 256-tile, '' when none)."""
+    n, i = changed(got, ref)
+    if not n:
+        return 0, ''
+    return n, (f'{tag}: {n} of {got.numel()} elements differ; first at {tile_of(i, tuple(got.shape))}: '
+               f'got {float(got.flatten()[i]):.6g} ref {float(ref.flatten()[i]):.6g}')
+
+
 def note(family, ratio):
     if math.isfinite(ratio):
         RATIOS[family] = max(RATIOS.get(family, 0.0), ratio)
@@ -191,7 +203,9 @@ def attn_bounds(q, k, v, dO, O, scale, keep=None, up=U16, r_out=U16, c=C_ATTN, b
       O   : c up (P~|V|) + r_out |O|                      (P~ = P * keep)
       dV  : c up (P~^T |dO|) + r_out |dV|
       dQ  : scale c up (P o (keep |dO||V|^T + Dabs)) |K| + r_out |dQ|,  dK likewise with |Q|
-    where Dabs = sum |dO| |O| bounds the row term Delta = sum dO O (the kernel forms it from its own rounded O)."""
+    where Dabs = sum |dO| |O| bounds the row term Delta = sum dO O (the kernel forms it from its own rounded O).
+      dS  : c up S + 4 u |dS| + 2^-126 (|dO||V|^T + Dabs) — a P below the smallest normal fp32 (a logit masked by -100) may be
+            flushed to 0, an absolute error of at most 2^-126 in P times |dP - Delta|."""
     P, s = softmax64(q, k, scale, bias)
     q64, k64, v64 = (t.detach().double() for t in (q, k, v))
     Pk = P if keep is None else P * keep.double()
@@ -220,8 +234,86 @@ def attn_bounds(q, k, v, dO, O, scale, keep=None, up=U16, r_out=U16, c=C_ATTN, b
                bdq=scale * c * up * (S @ k64.abs()) + r_out * dq.abs(),
                bdk=scale * c * up * (S.transpose(-2, -1) @ q64.abs()) + r_out * dk.abs(),
                bdv=c * up * (Pk.transpose(-2, -1) @ d64.abs()) + r_out * dv.abs(),
-               dS=dS, bdS=c * up * S + 4 * U32 * dS.abs())
+               dS=dS, bdS=c * up * S + 4 * U32 * dS.abs() + FLT_MIN * (mag + Dabs))
     return out
+
+
+def sum_bound(abs_sum, n, ref, out_dtype=torch.float32):
+    """An fp32 sum of n terms in ANY order (sequential, per-lane partials + shuffles, atomics): |fl(sum) - sum| <= (n - 1) u sum|t_i|
+    + O(u^2), taken as n u sum|t_i|; plus the rounding of the stored value, r_out |ref|.  A prefill the kernel adds to, and a
+    scale applied to the sum, count as one term each.  ``abs_sum`` = sum|t_i| (float64), n a number or a tensor per element."""
+    return n * U32 * torch.as_tensor(abs_sum).double() + out_round(out_dtype) * ref.detach().double().abs()
+
+
+def f32_attn_up(q, k, scale, bias=None, dv=None):
+    """Relative error allowance of P (and of what rides on it) in the fp32 attention kernels (up of ``attn_bounds``; r_out
+    out_round(fp32)).  A logit s = scale q.k (+ bias) is a d-term fp32 dot product: |ds| <= d u scale (|q||k|^T) + u |s|; P = exp(s -
+    lse) takes |ds| + |dlse| <= 2 max|ds| as a relative error, the exp a few u; the sums over the Nk keys (l, P.V, dP) and over the dv
+    value columns (dP, Delta) add Nk u and dv u.  So up = u (2 d scale max(|q||k|^T) + 2 max|s| + Nk + dv + 8) — max over all rows."""
+    q64, k64 = q.detach().double(), k.detach().double()
+    d, Nk = q64.shape[-1], k64.shape[-2]
+    s = (q64 @ k64.transpose(-2, -1)) * scale
+    if bias is not None:
+        s = s + bias.double()
+    mag = float((q64.abs() @ k64.abs().transpose(-2, -1)).max())
+    return U32 * (2 * d * scale * mag + 2 * float(s.abs().max()) + Nk + (d if dv is None else dv) + 8)
+
+
+def patchify64(img):
+    """[B, C, H, W] -> float64 [B, L, 256 C] 16 x 16 patches, channel fastest (the loss kernels' and the oracle's order)"""
+    B, C, H, W = img.shape
+    x = img.detach().double().reshape(B, C, H // 16, 16, W // 16, 16)
+    return x.permute(0, 2, 4, 3, 5, 1).reshape(B, (H // 16) * (W // 16), 256 * C)
+
+
+def mse_bounds(img, pred, mask, norm):
+    """Float64 AVMAE.patchify + forward_loss (per-patch mean, unbiased variance, eps 1e-6 inside the sqrt) and elementwise bounds
+    of what dav_patch_mse_fwd writes, from the magnitudes of one patch's P = 256 C target values t and predictions:
+      tmean  : e_m = u (P mean|t| + |m|)                                          (P-term sum, one division)
+      var    : Σ(t - m~)^2 = Σ(t - m)^2 + P (m - m~)^2 exactly, so e_q = (P + 3) u (q + P e_m^2) + P e_m^2   (q = Σ(t - m)^2)
+      trstd  : r = (q / (P - 1) + 1e-6)^-1/2, dr/dq = -r^3 / (2 (P - 1)): e_r = r^3 e_q / (2 (P - 1)) + 4 u r
+      x = pred - (t - m) r: e_x = |t - m| e_r + r e_m + 3 u (|pred| + |t - m| r)
+      loss_patch = mean x^2: (2 Σ|x| e_x + Σ e_x^2) / P + (P + 2) u mean x^2
+      loss = Σ(loss_patch mask) / Σ mask: (Σ e_lp mask + (n + 2) u Σ|loss_patch mask|) / Σ mask   (n = B L);  mask_sum exact.
+    Without norm m = 0 and r = 1 exactly.  pred [B, L, P], mask [B, L]."""
+    t = patchify64(img)
+    p64, m64 = pred.detach().double().reshape(t.shape), mask.detach().double().reshape(t.shape[:2])
+    P = t.shape[-1]
+    if norm:
+        m = t.mean(-1, keepdim=True)
+        q = ((t - m) ** 2).sum(-1, keepdim=True)
+        r = (q / (P - 1) + 1e-6).rsqrt()
+        e_m = U32 * (P * t.abs().mean(-1, keepdim=True) + m.abs())
+        e_q = (P + 3) * U32 * (q + P * e_m ** 2) + P * e_m ** 2
+        e_r = r ** 3 * e_q / (2 * (P - 1)) + 4 * U32 * r
+    else:
+        m, r = torch.zeros_like(t[..., :1]), torch.ones_like(t[..., :1])
+        e_m, e_r = torch.zeros_like(m), torch.zeros_like(r)
+    c = t - m
+    x = p64 - c * r
+    e_x = c.abs() * e_r + r * e_m + 3 * U32 * (p64.abs() + c.abs() * r)
+    lp = (x ** 2).mean(-1)
+    b_lp = (2 * (x.abs() * e_x).sum(-1) + (e_x ** 2).sum(-1)) / P + (P + 2) * U32 * lp
+    ms = m64.sum()
+    loss = (lp * m64).sum() / ms
+    b_loss = ((b_lp * m64).sum() + (lp.numel() + 2) * U32 * (lp * m64).abs().sum()) / ms
+    return dict(loss_patch=lp, tmean=m.squeeze(-1), trstd=r.squeeze(-1), bloss_patch=b_lp, btmean=e_m.squeeze(-1),
+                btrstd=e_r.squeeze(-1), loss=loss, bloss=b_loss, mask_sum=ms)
+
+
+def mse_grad(img, pred, mask, tmean, trstd, mask_sum, gout, out_dtype):
+    """Float64 reference and bound of dav_patch_mse_bwd(_f32) from the kernel's own statistics (tmean / trstd / mask_sum of the
+    forward): d pred = mask gout 2 / (P mask_sum) (pred - (t - tmean) trstd).  Eight fp32 roundings along the way (three for the
+    coefficient, t - m, x r, pred - .., two products), relative to |pred| + |t - m| r:  8 u |coef mask| (|pred| + |t - m| r) +
+    r_out |ref|.  Rows with mask 0 must come out exactly 0 (their bound is 0)."""
+    t = patchify64(img)
+    p64 = pred.detach().double().reshape(t.shape)
+    m64 = mask.detach().double().reshape(t.shape[:2] + (1,))
+    tm, tr = tmean.detach().double().reshape(m64.shape), trstd.detach().double().reshape(m64.shape)
+    coef = m64 * float(gout) * 2 / (t.shape[-1] * float(mask_sum))
+    c = (t - tm).abs() * tr
+    ref = coef * (p64 - (t - tm) * tr)
+    return ref, 8 * U32 * coef.abs() * (p64.abs() + c) + out_round(out_dtype) * ref.abs()
 
 
 def gang(probs):

@@ -148,3 +148,168 @@ def test_prefilled_accumulators_must_add_to_the_prefill():
     bound = K.gemm_bound(A.t(), Bm.t(), ref, torch.float32)
     assert K.within((pre.double() + prod).float(), ref, bound)[0]
     assert not K.within(prod.float(), ref, bound)[0]
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def test_unshuffle_bwd_reduce_that_overwrites_instead_of_accumulating():
+    """dpos / dmask_token are accumulated (+=).  The old check passed zeros: a kernel that WROTE its sums passes it; into a random
+    prefill it is off by the prefill."""
+    B, L, nk, D = 3, 24, 5, 64
+    gx = torch.randn(B, L, D, generator=_gen(20)).double()
+    restore = torch.stack([torch.randperm(L, generator=_gen(21 + b)) for b in range(B)])
+    msk = (restore >= nk).double().unsqueeze(-1)
+    sums = {'dpos': (gx.sum(0), gx.abs().sum(0), B), 'dmask_token': ((gx * msk).sum((0, 1)), (gx * msk).abs().sum((0, 1)), B * L)}
+    for name, (s, a, n) in sums.items():
+        right = lambda pre: (pre + s).float()                   # noqa: E731  the contract
+        wrong = lambda pre: s.float()                           # noqa: E731  a kernel that overwrites
+        zero = torch.zeros(s.shape, dtype=torch.float64)
+        assert gpu_selfcheck.rel(right(zero), s) <= 1e-5 and gpu_selfcheck.rel(wrong(zero), s) <= 1e-5    # old check: both pass
+        pre = K.prefilled(tuple(s.shape), seed=22).double()
+        ref = pre + s
+        bound = K.sum_bound(pre.abs() + a, n + 1, ref)
+        assert K.within(right(pre), ref, bound)[0]
+        assert not K.within(wrong(pre), ref, bound)[0], name
+
+
+def test_two_loss_patch_entries_swapped():
+    """patch_mse_fwd: only the scalar loss was compared.  Swapping two masked rows' loss_patch leaves it unchanged."""
+    B, C, H, W = 3, 3, 64, 96
+    L, P = (H // 16) * (W // 16), 256 * C
+    img, pred = torch.randn(B, C, H, W, generator=_gen(23)), torch.randn(B, L, P, generator=_gen(24))
+    mask = (torch.rand(B, L, generator=_gen(25)) > 0.3).float()
+    M = K.mse_bounds(img, pred, mask, True)
+    lp = M['loss_patch'].float()
+    loss = float((lp.double() * mask.double()).sum() / mask.double().sum())
+    assert abs(loss - float(M['loss'])) / float(M['loss']) <= 1e-5 and K.within(lp, M['loss_patch'], M['bloss_patch'])[0]
+    i, j = [int(x) for x in mask.flatten().nonzero()[:2, 0]]
+    bad = lp.clone().flatten()
+    bad[i], bad[j] = lp.flatten()[j], lp.flatten()[i]
+    bad = bad.view(B, L)
+    loss_bad = float((bad.double() * mask.double()).sum() / mask.double().sum())
+    assert abs(loss_bad - float(M['loss'])) / float(M['loss']) <= 1e-5        # old check: the scalar is unchanged
+    ok, _, msg = K.within(bad, M['loss_patch'], M['bloss_patch'], 'loss_patch')
+    assert not ok and '2 of' in msg
+
+
+def test_mse_bounds_edges():
+    """a constant patch (variance 0: rstd = 1 / sqrt(1e-6)), norm off (mean 0 and rstd 1 exactly), masked-out rows of the
+    gradient exactly 0"""
+    img, pred = torch.randn(2, 1, 32, 32, generator=_gen(26)), torch.randn(2, 4, 256, generator=_gen(27))
+    img[0, :, :16, :16] = 0.3
+    mask = torch.tensor([[1., 0., 1., 1.], [1., 1., 1., 1.]])
+    M = K.mse_bounds(img, pred, mask, True)
+    assert abs(float(M['trstd'][0, 0]) - 1e3) < 1e-6 and float(M['btrstd'][0, 0]) < 1e-2 * 1e3
+    M0 = K.mse_bounds(img, pred, mask, False)
+    assert float(M0['btmean'].abs().max()) == 0.0 and bool((M0['trstd'] == 1).all())
+    ref, bnd = K.mse_grad(img, pred, mask, M['tmean'].float(), M['trstd'].float(), mask.sum(), 0.7, BF16)
+    assert float(ref[0, 1].abs().max()) == 0.0 and float(bnd[0, 1].max()) == 0.0
+    assert K.within(ref.to(BF16), ref, bnd)[0]
+    bad = ref.to(BF16).clone()
+    bad[0, 1, 17] = 1e-30                                           # a masked-out row must be exactly 0
+    assert not K.within(bad, ref, bnd)[0]
+
+
+def test_one_wrong_pixel_in_patch_gather_at_the_bench_shape():
+    """patch_gather at the bench image shape (B 64, 224 x 224, 49 kept) was checked at rel 4e-3: one pixel swapped with its
+    neighbour passes it; the bit-exact check names it."""
+    B, C, H, W, nk = 64, 3, 224, 224, 49
+    L = (H // 16) * (W // 16)
+    img = torch.randn(B, C, H, W, generator=_gen(28))
+    ids = torch.stack([torch.randperm(L, generator=_gen(29 + b))[:nk] for b in range(B)])
+    cols = img.reshape(B, C, H // 16, 16, W // 16, 16).permute(0, 2, 4, 1, 3, 5).reshape(B, L, C * 256)
+    ref = cols.gather(1, ids.unsqueeze(-1).expand(-1, -1, C * 256)).reshape(B * nk, -1)
+    good = ref.to(BF16)
+    assert gpu_selfcheck.rel(good, ref) <= 4e-3 and K.exact(good, ref.to(BF16)) == (0, '')
+    bad = good.clone()
+    bad[1000, 300], bad[1000, 301] = good[1000, 301], good[1000, 300]
+    assert gpu_selfcheck.rel(bad, ref) <= 4e-3                                  # old check: passes
+    n, msg = K.exact(bad, ref.to(BF16), 'A')
+    assert n == 2 and '[1000, 300]' in msg
+
+
+def _window_case(B=2, nW=4, H=2, A=16, nF=9, d=32, seed=30):
+    N = A + nF
+    g = _gen(seed)
+    q, k, v, dO = (torch.randn(B * nW, H, N, d, generator=g).to(BF16) for _ in range(4))
+    bias = torch.zeros(B * nW, H, N, N)
+    bias[:, :, :A, :A] = torch.randn(B * nW, H, A, A, generator=g) * 0.7
+    return q, k, v, dO, bias, d ** -0.5
+
+
+def test_one_wrong_ds_entry_in_window_attention():
+    """attn_bias_bwd's dS was compared at rel 2e-2: one entry off by twice its bound passes it; attn_bounds' bdS does not."""
+    q, k, v, dO, bias, scale = _window_case()
+    O = K.attn_bounds(q, k, v, None, None, scale, bias=bias)['O'].to(BF16)
+    r = K.attn_bounds(q, k, v, dO, O, scale, bias=bias)
+    dS = r['dS'].float()
+    assert gpu_selfcheck.rel(dS, r['dS']) <= 2e-2 and K.within(dS, r['dS'], r['bdS'])[0]
+    i = int(r['dS'].abs().flatten().argsort()[r['dS'].numel() // 2])          # an entry of median magnitude
+    bad = dS.clone().flatten()
+    bad[i] += 2 * float(r['bdS'].flatten()[i])
+    bad = bad.view(dS.shape)
+    assert gpu_selfcheck.rel(bad, r['dS']) <= 2e-2                              # old check: passes
+    ok, ratio, _ = K.within(bad, r['dS'], r['bdS'], 'dS')
+    assert not ok and 1.5 < ratio < 2.5
+
+
+def test_window_fold_fusion_row_summed_over_one_window_less():
+    """window_fold's fusion rows are res + (1 / nW) sum over the nW windows, checked at rel 1e-6 over the whole output: a sum that
+    skips one window where that window's term is small (here 1e-4) passes it; the nW-term sum bound does not."""
+    B, nW, A, nF, C = 2, 4, 16, 9, 96
+    N, L = A + nF, nW * A
+    t = torch.randn(B, nW, N, C, generator=_gen(31))
+    res = torch.randn(B, nF + L, C, generator=_gen(32))
+    t[1, 2, A + 5, 40] = 1e-4
+    fs = 1.0 / nW
+    f64 = res[:, :nF].double() + fs * t[:, :, A:].double().sum(1)
+    bound = K.sum_bound(res[:, :nF].double().abs() + fs * t[:, :, A:].double().abs().sum(1), nW + 2, f64)
+    tok = t[:, :, :A].reshape(B, L, C).double() + res[:, nF:].double()
+    right = f64.float()
+    bad = right.clone()
+    bad[1, 5, 40] = float(f64[1, 5, 40] - fs * 1e-4)                           # window 2 skipped in this element
+    full = lambda f: torch.cat([f.double(), tok], 1)                            # noqa: E731
+    want = torch.cat([f64, tok], 1)
+    assert gpu_selfcheck.rel(full(right), want) <= 1e-6 and K.within(right, f64, bound)[0]
+    assert gpu_selfcheck.rel(full(bad), want) <= 1e-6                           # old check: passes
+    ok, ratio, msg = K.within(bad, f64, bound, 'fusion rows')
+    assert not ok and ratio > 1.0 and '[1, 5, 40]' in msg
+
+
+def test_unshuffle_fwd_writing_into_the_leading_rows():
+    """unshuffle_fwd writes rows nF.. of each batch element; the old check read only those rows of a zero-filled buffer, so a
+    kernel that also zero-fills (or writes) the nF leading rows passes it.  In a poisoned buffer the leading rows must keep their bits."""
+    B, L, nk, D, nF = 3, 24, 5, 64, 3
+    emb, mt, pos = torch.randn(B * nk, D, generator=_gen(33)), torch.randn(D, generator=_gen(34)), torch.randn(L, D, generator=_gen(35))
+    restore = torch.stack([torch.randperm(L, generator=_gen(36 + b)) for b in range(B)])
+    full = torch.cat([emb.view(B, nk, D), mt.view(1, 1, D).expand(B, L - nk, D)], 1)
+    want = full.gather(1, restore.unsqueeze(-1).expand(-1, -1, D)) + pos
+    lead = torch.zeros(B, nF + L, dtype=torch.bool)
+    lead[:, :nF] = True
+    old, new = torch.zeros(B, nF + L, D), K.poisoned((B, nF + L, D), torch.float32)
+    before = new.clone()
+    for out in (old, new):
+        out[:, nF:] = want
+        out[2, 1] = 0.0                                                         # ... and one leading row
+    assert gpu_selfcheck.rel(old[:, nF:], want) <= 1e-6 and K.exact(new[:, nF:], want) == (0, '')
+    assert K.changed(new, before, lead) == (D, (2 * (nF + L) + 1) * D)
+    good = before.clone()
+    good[:, nF:] = want
+    assert K.changed(good, before, lead) == (0, -1)
+
+
+def test_f32_attention_bound_is_tight():
+    """the fp32 twins' allowance (kcheck.f32_attn_up) stays well below bf16's one rounding: an O off by three times its fp32 bound —
+    which the bf16 bound would pass — fails it"""
+    q, k, v, dO, bias, scale = _window_case(seed=37)
+    q, k, v = q.float(), k.float(), v.float()
+    up = K.f32_attn_up(q, k, scale, bias)
+    assert up < K.U16 / 20
+    r = K.attn_bounds(q, k, v, None, None, scale, up=up, r_out=K.out_round(torch.float32), bias=bias)
+    O = r['O'].float()
+    assert K.within(O, r['O'], r['bO'])[0]
+    bad = (r['O'] + 3 * r['bO']).float()
+    assert K.within(bad, r['O'], K.attn_bounds(q, k, v, None, None, scale, bias=bias)['bO'])[0]
+    assert not K.within(bad, r['O'], r['bO'])[0]
