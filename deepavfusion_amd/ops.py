@@ -593,3 +593,61 @@ def cast_transpose_grouped(pairs):
     for q, (x, y) in zip(arr, pairs):
         q.x, q.y_bf16, q.R, q.C = _ptr(x), _ptr(y), int(x.shape[0]), int(x.shape[1])
     _lib.check(_lib.load().dav_cast_transpose_grouped(arr, len(pairs), _stream()), 'dav_cast_transpose_grouped')
+
+
+# ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------------------------------------
+
+KNN_TILE = 128          # queries per workgroup and bank rows per tile of dav_knn_topk_f32
+
+
+def knn_splits(Nq, N):
+    """Bank splits of dav_knn_topk_f32 that give the grid at least 2 x 256 workgroups (the header's suggested count)."""
+    qt, nt = -(-Nq // KNN_TILE), -(-N // KNN_TILE)
+    return max(1, min(nt, -(-512 // qt)))
+
+
+def knn_workspace_bytes(Nq, V, k, splits):
+    """splits * V * Nq * k * 8: one (score, index) list per split, view and query (include/dav_kernels.h)."""
+    return splits * V * Nq * k * 8
+
+
+def mean_l2n(x, out=None):
+    """F.normalize(x.mean(1), p=2, dim=1) of a fp32 [B, L, D] view with unit column stride (dav_mean_l2n_f32)."""
+    B, L, D = x.shape
+    if x.dtype != F32 or x.stride(2) != 1:
+        raise ValueError('mean_l2n needs fp32 [B, L, D] with unit column stride')
+    out = torch.empty(B, D, dtype=F32, device=x.device) if out is None else out
+    _lib.check(_lib.load().dav_mean_l2n_f32(_ptr(x), B, L, D, x.stride(1), x.stride(0), _ptr(out), _stream()), 'dav_mean_l2n_f32')
+    return out
+
+
+def knn_topk(queries, banks, k, sum_view=True, splits=None, out=None, workspace=None):
+    """Top-k bank rows of every query, per modality and (sum_view) for the sum of the modality scores (dav_knn_topk_f32).
+    queries / banks: 1-3 fp32 [Nq, D] / [N, D] tensors with unit column stride (a query tensor may be its bank); the sum view
+    is (s_0 + s_1) + s_2.  -> (values [V, Nq, k] fp32, indices [V, Nq, k] int64), V = len(queries) + sum_view."""
+    M = len(queries)
+    if M != len(banks) or not 1 <= M <= 3:
+        raise ValueError('knn_topk takes 1 to 3 (query, bank) pairs')
+    Nq, D = queries[0].shape
+    N = banks[0].shape[0]
+    for t in list(queries) + list(banks):
+        if t.dtype != F32 or t.dim() != 2 or t.shape[1] != D or t.stride(1) != 1:
+            raise ValueError('knn_topk needs fp32 [rows, D] operands with unit column stride')
+    if any(q.shape[0] != Nq or q.stride(0) != queries[0].stride(0) for q in queries) or \
+            any(x.shape[0] != N or x.stride(0) != banks[0].stride(0) for x in banks):
+        raise ValueError('all query (bank) tensors need the same rows and row stride')
+    V = M + int(bool(sum_view))
+    S = knn_splits(Nq, N) if splits is None else int(splits)
+    dev = queries[0].device
+    if out is None:
+        out = (torch.empty(V, Nq, k, dtype=F32, device=dev), torch.empty(V, Nq, k, dtype=torch.int32, device=dev))
+    nbytes = knn_workspace_bytes(Nq, V, k, S)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    qp = [_ptr(q) for q in queries] + [None] * (3 - M)
+    xp = [_ptr(x) for x in banks] + [None] * (3 - M)
+    _lib.check(_lib.load().dav_knn_topk_f32(qp[0], xp[0], qp[1], xp[1], qp[2], xp[2], M, Nq, N, D, queries[0].stride(0),
+                                            banks[0].stride(0), int(bool(sum_view)), int(k), S, _ptr(out[0]), _ptr(out[1]),
+                                            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+               'dav_knn_topk_f32')
+    return out[0], out[1].long()

@@ -1,0 +1,177 @@
+"""Nearest-neighbour probe of the pre-training worker: util/knn_probe.py of the reference (EvalAVNNProbe), on the MI355X path.
+
+Every eval clip is encoded (``model.forward_encoder(image, spec)[:3]``), its image, audio and fusion tokens are mean-pooled and
+L2-normalised (dav_mean_l2n_f32), gathered over the data-parallel group, and every clip is scored against every other in the three
+modalities and their sum by ONE call of the fused similarity + top-k kernel (dav_knn_topk_f32, k = 2, no score matrix in memory).
+As in the reference the prediction of a clip is the label of its 2nd neighbour (position 1: the 1st is normally the clip itself)
+and the metrics are ``{audio,image,fusion,all}_nn_acc`` (single-label) or ``_nn_ap`` / ``_nn_auc`` (multi-hot labels).
+
+Documented differences from the reference:
+  - the features come from the product bf16 engine — the same forward the training step runs; the reference's ``evaluate`` runs
+    its encoder in fp32 (it is called outside autocast).  The LayerNorm-folding path (DAV_LN_FUSE) is switched off for the
+    probe's forward, so it neither makes nor reads gamma-folded weight copies next to a captured training step;
+  - the scores are exact-fp32 FMA chains in the kernel's fixed order, ties go to the lower bank index (torch.topk leaves the
+    order of ties unspecified);
+  - the loader order is re-seeded at every call (the same clips, in the same order, at every epoch), and DataLoader workers
+    follow ``env.workers`` (the reference forces at least one);
+  - ``dataset=synthetic`` is a labelled synthetic set (seeded class prototypes + seeded noise); VGGSound / AudioSet need PyAV and
+    torchaudio, which are not dependencies of this project.  Python callers may pass any dataset that yields
+    ``(image, spec, {'class': label})`` — the reference's contract; multi-hot labels ([num_classes] per clip) select the AP / AUC
+    metrics.
+"""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from .. import engine as E
+from .. import ops
+from . import distributed as dist_utils
+
+MODALITIES = ('audio', 'image', 'fusion', 'all')          # the reference's key order
+_VIEW = {'image': 0, 'audio': 1, 'fusion': 2, 'all': 3}   # kernel views: modalities passed as (image, audio, fusion), sum = view 3
+
+
+class SyntheticLabelledAV(torch.utils.data.Dataset):
+    """Class c has a fixed seeded prototype frame (ImageNet-normalised scale, N(0, 1)) and log-mel patch (about [-7, 4]); clip i
+    is of class i % num_classes and is its prototype plus seeded Gaussian noise of std ``noise``."""
+
+    def __init__(self, n, num_classes, image_size, audio_size, seed=0, noise=0.5):
+        self.n, self.num_classes, self.seed, self.noise = n, num_classes, seed, noise
+        self.image_size, self.audio_size = tuple(image_size), tuple(audio_size)
+        g = torch.Generator().manual_seed(seed * 1_000_003 + 7919)
+        self.proto_image = torch.randn(num_classes, 3, *self.image_size, generator=g)
+        self.proto_audio = (torch.randn(num_classes, 1, *self.audio_size, generator=g) * 2.0 - 3.0).clamp(-7, 4)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        c = i % self.num_classes
+        g = torch.Generator().manual_seed(self.seed * 1_000_003 + 104_729 + i)
+        image = self.proto_image[c] + self.noise * torch.randn(3, *self.image_size, generator=g)
+        spec = self.proto_audio[c] + self.noise * torch.randn(1, *self.audio_size, generator=g)
+        return image, spec, {'class': c}
+
+
+# ---- metrics: sklearn.metrics.average_precision_score / roc_auc_score (average=None), restated -------------------------------
+
+def _binary_curve(y_true, y_score):
+    """sklearn's _binary_clf_curve: cumulative true / false positives at every DISTINCT score, scores descending (ties grouped)."""
+    order = np.argsort(y_score, kind='mergesort')[::-1]
+    y_score, y_true = y_score[order], y_true[order].astype(np.float64)
+    distinct = np.where(np.diff(y_score))[0]
+    thr = np.r_[distinct, y_true.size - 1]
+    tps = np.cumsum(y_true)[thr]
+    fps = 1 + thr - tps
+    return fps, tps
+
+
+def average_precision(y_true, y_score):
+    """Per-column AP of multi-hot labels [n, C] and scores [n, C]: sum over thresholds of (R_t - R_{t-1}) P_t."""
+    out = np.empty(y_true.shape[1])
+    for c in range(y_true.shape[1]):
+        fps, tps = _binary_curve(y_true[:, c], y_score[:, c])
+        precision = tps / (tps + fps)
+        recall = tps / tps[-1] if tps[-1] > 0 else np.ones_like(tps)
+        out[c] = np.sum(np.diff(np.r_[0.0, recall]) * precision)
+    return out
+
+
+def roc_auc(y_true, y_score):
+    """Per-column ROC AUC (trapezoids over the distinct-threshold curve from (0, 0)); a column with one class only is an error,
+    as in sklearn."""
+    out = np.empty(y_true.shape[1])
+    for c in range(y_true.shape[1]):
+        fps, tps = _binary_curve(y_true[:, c], y_score[:, c])
+        if tps[-1] <= 0 or fps[-1] <= 0:
+            raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+        fpr, tpr = np.r_[0.0, fps / fps[-1]], np.r_[0.0, tps / tps[-1]]
+        out[c] = np.sum(np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2)
+    return out
+
+
+def probe_metrics(preds, labels, multi_label):
+    """util/knn_probe.py:133-150: preds = {modality: (predicted labels [n] or [n, C], neighbour score [n])} (numpy), labels [n]
+    or multi-hot [n, C] -> {'<mod>_nn_acc'} or {'<mod>_nn_ap', '<mod>_nn_auc'} in the order of ``preds``."""
+    out = OrderedDict()
+    if multi_label:
+        seen = labels.sum(0) > 0
+        for mod, (ypred, yscore) in preds.items():
+            scores = ypred * yscore[:, None]
+            out[f'{mod}_nn_ap'] = float(average_precision(labels[:, seen], scores[:, seen]).mean())
+            out[f'{mod}_nn_auc'] = float(roc_auc(labels[:, seen], scores[:, seen]).mean())
+    else:
+        for mod, (ypred, _) in preds.items():
+            out[f'{mod}_nn_acc'] = float(np.mean(ypred == labels) * 100)
+    return dict(out)
+
+
+def knn_predictions(v_feats, a_feats, mm_feats, labels, k=2):
+    """util/knn_probe.py:113-131 as ONE kernel call: -> {modality: (labels of the 2nd neighbour, its score)} (device tensors)."""
+    val, idx = ops.knn_topk((v_feats, a_feats, mm_feats), (v_feats, a_feats, mm_feats), k=k, sum_view=True)
+    return OrderedDict((mod, (labels[idx[_VIEW[mod], :, 1]], val[_VIEW[mod], :, 1])) for mod in MODALITIES)
+
+
+class EvalAVNNProbe:
+    def __init__(self, probe_args, log_args, env_args, dataset=None):
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.distributed = dist_utils.get_world_size() > 1
+        self.eval_freq = int(log_args.eval_freq)
+        self.print_freq = int(log_args.print_freq)
+        self.dataset = probe_args.get('dataset') if dataset is None else 'custom'
+        self.seed = int(env_args.get('seed') or 0)
+        if dataset is not None:
+            self.db, self.multi_label = dataset, None          # decided by the label shape
+        elif self.dataset == 'synthetic':
+            image_size = (int(probe_args.image_size),) * 2
+            audio_size = (int(probe_args.audio_mels), int(float(probe_args.audio_dur) * 64))
+            self.db = SyntheticLabelledAV(int(probe_args.num_samples), int(probe_args.num_classes), image_size, audio_size,
+                                          seed=self.seed)
+            self.multi_label = False
+        elif self.dataset in ('vggsound', 'audioset'):
+            raise NotImplementedError(f'nn_probe.dataset={self.dataset}: only nn_probe.dataset=synthetic is on the MI355X path '
+                                      '(the reference datasets need PyAV/torchaudio)')
+        else:
+            raise NotImplementedError(f'nn_probe.dataset={self.dataset}')
+        if self.distributed:
+            self.generator = None
+            self.sampler = torch.utils.data.DistributedSampler(self.db, num_replicas=dist_utils.get_world_size(),
+                                                               rank=dist_utils.get_rank(), shuffle=True, seed=self.seed)
+        else:
+            self.generator = torch.Generator()
+            self.sampler = torch.utils.data.RandomSampler(self.db, generator=self.generator)
+        self.loader = torch.utils.data.DataLoader(self.db, sampler=self.sampler, batch_size=max(int(probe_args.batch_size) // 4, 1),
+                                                  num_workers=int(env_args.get('workers') or 0), pin_memory=False, drop_last=True)
+
+    @torch.no_grad()
+    def extract(self, model):
+        """util/knn_probe.py:84-111: -> normalised (image, audio, fusion) features [n, D] and labels, gathered over the group."""
+        model.train(False)
+        if self.distributed:
+            self.sampler.set_epoch(0)
+        else:
+            self.generator.manual_seed(self.seed)
+        feats, labels = ([], [], []), []
+        prev = E.LN_FUSE_MODE
+        E.set_ln_fuse('off')
+        try:
+            for image, spec, anno in self.loader:
+                spec = spec.to(self.device, non_blocking=True).float()
+                image = image.to(self.device, non_blocking=True).float()
+                lbl = anno['class'].to(self.device, non_blocking=True).long()
+                for f, x in zip(feats, model.forward_encoder(image, spec)[:3]):      # x_v, x_a, x_mm
+                    f.append(ops.mean_l2n(x))
+                labels.append(lbl)
+        finally:
+            E.set_ln_fuse(prev)
+        v_feats, a_feats, mm_feats = (dist_utils.concat_all_gather(torch.cat(f)) for f in feats)
+        return v_feats, a_feats, mm_feats, dist_utils.concat_all_gather(torch.cat(labels))
+
+    @torch.no_grad()
+    def evaluate(self, model, epoch=0):
+        v_feats, a_feats, mm_feats, labels = self.extract(model)
+        preds = knn_predictions(v_feats, a_feats, mm_feats, labels)
+        multi_label = self.multi_label if self.multi_label is not None else labels.dim() == 2
+        return probe_metrics(OrderedDict((m, (p.cpu().numpy(), s.cpu().numpy())) for m, (p, s) in preds.items()),
+                             labels.cpu().numpy(), multi_label)

@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 extern "C" {
 #endif
 
-#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) */
+#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) (9 also: dav_mean_l2n_f32, dav_knn_topk_f32) */
 int dav_abi_version(void);
 int dav_build_flags(void);   /* bit 0: experimental build (make EXPERIMENTAL=1): the rejected GEMM tile configurations exist */
 /* text of the last HIP error latched by a kernel launch of the calling thread (diagnostics) */
@@ -361,6 +361,26 @@ int dav_logmel(const float* wave, int B, int S, int n_fft, int hop, int n_mels, 
                const float* sin_tab, const float* fbank, const int* band_lo, const int* band_hi, float eps, int apply_log,
                int drop_last, float* out, hipStream_t stream);
 int dav_log10_eps(const float* x, float eps, long n, float* y, hipStream_t stream);      /* aT.Log: y = log10(x + eps) */
+
+/* ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------- */
+/* out[b, :] = v / max(||v||_2, 1e-12) with v = mean over l of x[b, l, :]: the x.mean(dim=1) + F.normalize(p=2, dim=1) of
+ * util/knn_probe.py:102-110.  x fp32 [B, L, D] with row stride ld_row (>= D) and batch stride ld_batch (elements); out dense
+ * fp32 [B, D].  The mean is a sequential fp32 sum over l divided by L; an all-zero v gives zeros. */
+int dav_mean_l2n_f32(const float* x, int B, int L, int D, long ld_row, long ld_batch, float* out, hipStream_t stream);
+/* Fused similarity + top-k of util/knn_probe.py:117-131 (the einsum('qd,nd->qn') of each modality, scores_v + scores_a + scores_mm,
+ * torch.topk(k, sorted=True)), without a score matrix in memory.  M in {1, 2, 3} modality pairs (q_m [Nq, D] row stride ldq,
+ * x_m [N, D] row stride ldx, fp32; q_m may alias x_m): s_m(i, n) = sum_d q_m[i, d] x_m[n, d] as an fp32 FMA chain (exact-fp32 MFMA,
+ * no rounding of the operands).  sum_view = 1 adds view M: s(i, n) = (s_0 + s_1) + s_2 (pass image, audio, fusion in that order
+ * for the reference's sum).  Outputs top_val [V, Nq, k] fp32 and top_idx [V, Nq, k] int32, V = M + sum_view, each row sorted by
+ * score descending, ties to the LOWER bank index; no self-exclusion (the probe reads position 1).  NaN scores are never selected.
+ * 1 <= k <= min(8, N); D % 4 == 0; q_m / x_m 16-byte aligned, ldq / ldx multiples of 4 (else -5).
+ * The bank is cut into `splits` (1 .. 65535) runs of 128-row tiles, each keeping its own top-k list in the workspace, and a second
+ * launch merges them: workspace_bytes >= splits * V * Nq * k * 8 (8-byte aligned).  The result is bitwise the same for every split
+ * count and every chunking of the queries.  Suggested split count (deepavfusion_amd.ops.knn_splits): enough workgroups to cover
+ * the 256 CUs twice, splits = min(ceil(N / 128), max(1, ceil(512 / ceil(Nq / 128)))). */
+int dav_knn_topk_f32(const float* q0, const float* x0, const float* q1, const float* x1, const float* q2, const float* x2, int M,
+                     int Nq, int N, int D, long ldq, long ldx, int sum_view, int k, int splits, float* top_val, int* top_idx,
+                     void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ---- fp32-operand twins (csrc/f32_path.hip) ------------------------------------------------ */
 /* The same contracts as the bf16 entry points above with every operand, second output and intermediate in fp32 (plain

@@ -63,7 +63,9 @@ def load_config(name='deepavfusion', overrides=()):
             if isinstance(v, dict):
                 resolve(v)
             elif isinstance(v, str) and '${' in v:
-                node[k] = re.sub(r'\$\{([^}]+)\}', lambda m: str(lookup(m.group(1))), v)
+                whole = re.fullmatch(r'\$\{([^}]+)\}', v)
+                # a value that is one interpolation keeps the type of what it names (omegaconf does the same); text around it makes a string
+                node[k] = lookup(whole.group(1)) if whole else re.sub(r'\$\{([^}]+)\}', lambda m: str(lookup(m.group(1))), v)
     resolve(cfg)
     return cfg
 
@@ -147,6 +149,11 @@ def main_worker(local_rank, args):
         B = args.opt.batch_size
         graphed = misc_utils.GraphedStep(trainer, (B, 3, *image_size), (B, 1, *audio_size), clip_grad=args.opt.clip_grad)
 
+    knn_probe = None
+    if args.get('nn_probe') and args.nn_probe.get('dataset'):          # train.py:116-117 (nn_probe.dataset=null: no probe)
+        from deepavfusion_amd.util.knn_probe import EvalAVNNProbe
+        knn_probe = EvalAVNNProbe(args.nn_probe, args.log, args.env)
+
     frontend = None
     if gpu_frontend:
         from deepavfusion_amd.util.audio_transforms import LogMelSpectrogram
@@ -158,6 +165,9 @@ def main_worker(local_rank, args):
         train_one_epoch(loader, trainer, epoch, device, args, graphed, frontend)
         if graphed is not None:
             graphed.check()          # never write a checkpoint behind a skipped (non-finite) captured step: raise like train.py:166-167
+        if knn_probe is not None and (epoch % args.log.eval_freq == 0 or epoch == args.opt.epochs - 1 or epoch == start_epoch):
+            knn_stats = knn_probe.evaluate(trainer.eval_model, epoch=epoch)             # train.py:129-132
+            print(f'[NN-probe][Ep-{epoch}/{args.opt.epochs}] {knn_stats}')
         ckpt.checkpoint(epoch + 1, {'epoch': epoch + 1})
 
 
