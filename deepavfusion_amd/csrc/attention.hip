@@ -25,6 +25,7 @@
 #include <cstdlib>
 static int attn_debug() { static const int v = [] { const char* e = getenv("DAV_ATTN_DEBUG"); return e ? atoi(e) : 0; }(); return v; }
 int dav_attn_qt = 0;      // dav_tune knob 3: 0 = auto, 1 / 2 = query tiles per wave in the forward kernel
+int dav_attn_onepass = 0; // dav_tune knob 5: 0 = the rule (onepass_fits), 1 = always the dQ + dK/dV kernels, 2 = one pass whenever it fits LDS
 
 namespace {
 
@@ -158,6 +159,7 @@ template <int RB> __device__ __forceinline__ bf16x8 lds_frag_tr(uint32_t a) {   
   u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, (uintptr_t)(a + 16 * RB)));
   return u.v;
 }
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 lds_f4(uint32_t a) { return *LDS_PTR(const f32x4, (uintptr_t)a); }
 
 __device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
@@ -762,6 +764,189 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, const int
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward in ONE pass (short problems: the towers' 49..95-row self-attention, the fusion block's aggregations and pair attention)
+// ------------------------------------------------------------------------------------------------
+// Q, dO, K of the (batch, head) are staged once (a wave's V rows come straight from global memory: only its own key tile reads
+// them, and without a V tile 80 x 112 rows still fit) and S, P, dP, dS are computed ONCE.  Phase A is the dK / dV walk: a wave owns a
+// 16-key tile, walks the query rows in ascending order and keeps dK, dV in registers; the dS it makes on the way (bf16, the same
+// pack8 rounding the dK MFMA reads) is also left, transposed, in an LDS patch.  After one barrier, phase B: a wave owns a 16-query
+// tile and accumulates dQ = dS.K over the key rows in ascending order from that patch.  Every (query tile, key tile) product has
+// exactly one owner in either phase, so there is no cross-wave reduction and no atomic: the sums have one fixed order.
+// Also writes Delta = rowsum(dO o O) (the same per-lane order as the dQ kernel) and zero-fills the dq_ctx rows.
+// dS^T patch: [Nqp / 32] blocks of [Nkp keys][32 query columns] bf16 (64-byte rows, the 64-byte row swizzle), so that the dQ
+// phase reads its B operand with the same transposing read as every other transposed fragment here.
+template <int DQK, int DV>
+__device__ __forceinline__ void attn_bwd_one_body(const AttnParams& p, const int bh) {
+  constexpr int DQKP = DQK < 32 ? 32 : DQK, QRB = DQKP * 2, KS = DQKP / 32, DVP = DV < 32 ? 32 : DV, ORB = DVP * 2, VS = DVP / 32, QC = DQK / 16, VC = DV / 16;
+  constexpr int SRB = 64;
+  // (1 KB-aligned, so that the fragment addresses of the column blocks of a tile differ from block 0's by an XOR: one address
+  // register per operand instead of one per operand and column block — what keeps this body inside 128 registers)
+  extern __shared__ __attribute__((aligned(1024))) char smem_one[];
+  char* smem = smem_one;
+  const int Nqp = (p.Nq + 31) & ~31, Nkp = (p.Nk + 31) & ~31;
+  char* Qs = smem;                      // [Nqp][DQKP]
+  char* dOs = Qs + Nqp * QRB;           // [Nqp][DVP]
+  char* Ks = dOs + Nqp * ORB;           // [Nkp][DQKP]
+  char* dSs = Ks + Nkp * QRB;           // [Nqp / 32][Nkp][32]
+  float* lse_s = reinterpret_cast<float*>(dSs + Nqp * Nkp * 2);       // [Nqp]
+  float* del_s = lse_s + Nqp;                                        // [Nqp]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  const int b = bh / p.H, h = bh % p.H;
+  const int fr = lane & 15, g = lane >> 4;
+
+  if (p.dq_ctx > 0) {                   // this head's dQ slots of the context-only rows (see AttnParams::dq_ctx)
+    constexpr int cpr = DQK / 8;
+    for (int c = tid; c < p.dq_ctx * cpr; c += blockDim.x) {
+      const int r = c / cpr, cc = c % cpr;
+      *reinterpret_cast<uint4*>(p.dQ + b * p.dq_bs + (long)(r - p.dq_ctx) * p.dq_rs + h * DQK + cc * 8) = uint4{0, 0, 0, 0};
+    }
+  }
+  stage_rows<DQK, DQKP>(Qs, p.Q + b * p.q_bs + h * DQK, p.Nq, Nqp, p.q_rs, tid, blockDim.x);
+  stage_rows<DV, DVP>(dOs, p.dO + b * p.do_bs + h * DV, p.Nq, Nqp, p.do_rs, tid, blockDim.x);
+  stage_rows<DQK, DQKP>(Ks, p.K + b * p.k_bs + h * DQK, p.Nk, Nkp, p.k_rs, tid, blockDim.x);
+  // the V rows of this wave's (first) key tile; rows past the last key are zero like the padded rows of the K tile
+  bf16x8 vf[VS];
+  auto load_v = [&](int kt) {
+    const int key = kt * 16 + fr;
+    const bf16_t* vrow = p.V + b * p.v_bs + (long)(key < p.Nk ? key : p.Nk - 1) * p.v_rs + h * DV;
+#pragma unroll
+    for (int kk = 0; kk < VS; ++kk) vf[kk] = gfrag(vrow, kk * 32 + 8 * g, key < p.Nk && kk * 32 + 8 * g < DV);
+  };
+  load_v(wave < (Nkp >> 4) ? wave : 0);
+  // Delta and the row statistics while the tiles are in flight (one wait for all of it)
+  for (int qt = wave; qt < (Nqp >> 4); qt += nw) {
+    const int q = qt * 16 + fr;
+    const bool ok = q < p.Nq;
+    const int qc = ok ? q : p.Nq - 1;
+    const bf16_t* dorow = p.dO + b * p.do_bs + (long)qc * p.do_rs + h * DV;
+    const bf16_t* orow = p.Of + b * p.o_bs + (long)qc * p.o_rs + h * DV;
+    float d = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < VS; ++kk) {
+      const bf16x8 dof = gfrag(dorow, kk * 32 + 8 * g, kk * 32 + 8 * g < DV);
+      const bf16x8 of = gfrag(orow, kk * 32 + 8 * g, kk * 32 + 8 * g < DV);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d += (float)dof[e] * (float)of[e];
+    }
+    d += __shfl_xor(d, 16, 64);
+    d += __shfl_xor(d, 32, 64);
+    if (g == 0) {
+      const long sidx = ((long)b * p.H + h) * p.Nq + qc;
+      lse_s[q] = ok ? p.LSE[sidx] * 1.44269504088896341f : 1e30f;     // log2 domain; 2^(s - 1e30) == 0 for padded query rows
+      del_s[q] = ok ? d : 0.f;
+      if (ok) p.Delta[sidx] = d;
+    }
+  }
+  stage_wait();
+  __syncthreads();
+
+  const float sl2 = p.scale * 1.44269504088896341f;
+  // ---- phase A: dK, dV of a key tile; dS^T into the patch.  All Nkp / 16 key tiles (the dQ phase reads every patch row; a tile
+  // past the last key works on zero K / V rows and stores nothing)
+  for (int kt = wave; kt < (Nkp >> 4); kt += nw) {
+    const int key = kt * 16 + fr;
+    bf16x8 kf[KS];
+    f32x4 dk[QC], dv[VC];
+    if (kt != wave) load_v(kt);           // (more than 8 key tiles: a second round pays its own global-memory latency)
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) kf[kk] = lds_frag(lds_addr(Ks) + frag_off<QRB>(fr, kk, g) + kt * 16 * QRB);
+#pragma unroll
+    for (int c = 0; c < QC; ++c) dk[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < VC; ++c) dv[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // column block kk of a row-major fragment: slot (4 kk + g) ^ swz = address ^ (kk << 6); column block c of a transposed one:
+    // slot (2 c + x) ^ swz = address ^ (c << 5)
+    uint32_t qa_ = lds_addr(Qs) + frag_off<QRB>(fr, 0, g), oa = lds_addr(dOs) + frag_off<ORB>(fr, 0, g);
+    uint32_t ota = lds_addr(dOs) + frag_tr_off<ORB>(0, lane), qta = lds_addr(Qs) + frag_tr_off<QRB>(0, lane);
+    uint32_t la = lds_addr(lse_s) + 16 * g, da = lds_addr(del_s) + 16 * g;     // this lane's four query rows' statistics
+    // patch row `key`, query columns 16 t + 4 g .. + 3 of the 32-column block: 8 bytes at slot 2 t + (g >> 1), half g & 1
+    const int swz = row_swz<SRB>(key);
+    uint32_t sa = lds_addr(dSs) + key * SRB + 8 * (g & 1);
+    for (int qa = 0; qa < Nqp; qa += 32) {
+      f32x4 s[2], dp[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        bf16x8 qf[KS], dof[VS];
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) qf[kk] = lds_frag((qa_ ^ (kk << 6)) + t * 16 * QRB);
+#pragma unroll
+        for (int kk = 0; kk < VS; ++kk) dof[kk] = lds_frag((oa ^ (kk << 6)) + t * 16 * ORB);
+        const f32x4 lse4 = lds_f4(la + t * 64), del4 = lds_f4(da + t * 64);
+        s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk], kf[kk], s[t], 0, 0, 0);
+#pragma unroll
+        for (int kk = 0; kk < VS; ++kk) dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof[kk], vf[kk], dp[t], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], sl2, -lse4[r]));
+          s[t][r] = pr;                               // P[q][key]
+          dp[t][r] = pr * (dp[t][r] - del4[r]);       // dS[q][key]
+        }
+      }
+      const bf16x8 pf = pack8(s[0], s[1]);
+      union { bf16x8 v; u32x2 h[2]; } ds;
+      ds.v = pack8(dp[0], dp[1]);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) *LDS_PTR(u32x2, (uintptr_t)(sa + (uint32_t)((((2 * t + (g >> 1)) ^ swz)) << 4))) = ds.h[t];
+#pragma unroll
+      for (int c = 0; c < VC; ++c) dv[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<ORB>(ota ^ (c << 5)), pf, dv[c], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < QC; ++c) dk[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<QRB>(qta ^ (c << 5)), ds.v, dk[c], 0, 0, 0);
+      qa_ += 32 * QRB; oa += 32 * ORB; ota += 32 * ORB; qta += 32 * QRB;
+      la += 128; da += 128;
+      sa += Nkp * SRB;
+    }
+    if (key < p.Nk) {
+      bf16_t* dkrow = p.dK + b * p.dk_bs + (long)key * p.dk_rs + h * DQK;
+      bf16_t* dvrow = p.dV + b * p.dv_bs + (long)key * p.dv_rs + h * DV;
+#pragma unroll
+      for (int c = 0; c < QC; ++c) {
+        uint2 w;
+        w.x = pack2bf(dk[c][0] * p.scale, dk[c][1] * p.scale);
+        w.y = pack2bf(dk[c][2] * p.scale, dk[c][3] * p.scale);
+        *reinterpret_cast<uint2*>(dkrow + c * 16 + 4 * g) = w;
+      }
+#pragma unroll
+      for (int c = 0; c < VC; ++c) {
+        uint2 w;
+        w.x = pack2bf(dv[c][0], dv[c][1]);
+        w.y = pack2bf(dv[c][2], dv[c][3]);
+        *reinterpret_cast<uint2*>(dvrow + c * 16 + 4 * g) = w;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- phase B: dQ of a query tile over all key rows (padded key rows: whatever dS they got multiplies zero K rows)
+  for (int qt = wave; qt < ((p.Nq + 15) >> 4); qt += nw) {
+    f32x4 dq[QC];
+#pragma unroll
+    for (int c = 0; c < QC; ++c) dq[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    uint32_t kta = lds_addr(Ks) + frag_tr_off<QRB>(0, lane);
+    uint32_t dsa = lds_addr(dSs) + (qt >> 1) * Nkp * SRB + frag_tr_off<SRB>((qt & 1) * 16, lane);
+    for (int k0 = 0; k0 < Nkp; k0 += 32) {
+      const bf16x8 dsf = lds_frag_tr<SRB>(dsa);
+#pragma unroll
+      for (int c = 0; c < QC; ++c) dq[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<QRB>(kta ^ (c << 5)), dsf, dq[c], 0, 0, 0);
+      kta += 32 * QRB;
+      dsa += 32 * SRB;
+    }
+    const int q = qt * 16 + fr;
+    if (q < p.Nq) {
+      bf16_t* dqrow = p.dQ + b * p.dq_bs + (long)q * p.dq_rs + h * DQK;
+#pragma unroll
+      for (int c = 0; c < QC; ++c) {
+        uint2 w;
+        w.x = pack2bf(dq[c][0] * p.scale, dq[c][1] * p.scale);
+        w.y = pack2bf(dq[c][2] * p.scale, dq[c][3] * p.scale);
+        *reinterpret_cast<uint2*>(dqrow + c * 16 + 4 * g) = w;
+      }
+    }
+  }
+}
+
 // Head pairing for narrow heads (round 3): with d = 32 a head's K / V / Q rows are 64-byte pieces of the fused qkv rows — every
 // 128-byte line is wanted by the workgroups of heads 2j and 2j+1.  Workgroup x runs on XCD x % 8, so neighbours in x never share
 // an L2; this permutation of the linear (batch, head) index puts heads 2j and 2j+1 on ids x and x + 8 — the same XCD, dispatched
@@ -774,7 +959,8 @@ __device__ __forceinline__ int pair_heads(int x, int n) {
 // (round 4 tried the backward as ONE kernel from one recomputation of the probabilities — a wave owning three key tiles, walking the
 // query tiles once, dS transposed through an LDS patch, the waves' partial dQ tiles reduced per 32-query step: correct and no faster
 // (352 x 352: 113 vs 117 us, 228 x 228: 72 vs 60 us, profiles/r04_attn_fused_bwd.txt): halving the exp / fma work moves the bound to the
-// LDS pipe at one workgroup per CU.  Removed in round 5; DESIGN_HISTORY section 11.)
+// LDS pipe at one workgroup per CU.  Removed in round 5; DESIGN_HISTORY section 11.  The SHORT problems are another regime — latency
+// of the launches and their staging waits, not arithmetic — and have attn_bwd_one_body above.)
 
 // ---- kernels: one grid per problem, or (resident variants) several problems in one grid (batch.h) ------------------
 template <int DQK, int DV, bool CHUNKED, int QT, bool DROP = false>
@@ -800,26 +986,33 @@ __global__ __launch_bounds__(512, (DQK <= 32 && DV <= 32 && !DROP) ? DKV32_MIN_B
   attn_bwd_dkv_body<DQK, DV, CHUNKED, CHUNKED ? 1 : bwd_tiles<DQK, DV>(), DROP>(p, (DQK <= 32 && p.pair) ? pair_heads(blockIdx.x, gridDim.x) : (int)blockIdx.x, blockIdx.y);
 }
 
+// the backward of a short problem in one launch (attn_bwd_one_body); 128 registers: two 8-wave workgroups per CU
+template <int DQK, int DV>
+__global__ __launch_bounds__(512, 4) void attn_bwd_onepass_kernel(AttnParams p) {
+  attn_bwd_one_body<DQK, DV>(p, (int)blockIdx.x);
+}
+
 constexpr int ATTN_GROUP_MAX = 8;
 struct AttnGroup {
   AttnParams prob[ATTN_GROUP_MAX];
   int first_block[ATTN_GROUP_MAX + 1];
   int count;
 };
-// WHICH: 0 forward, 1 dQ, 2 dK/dV.  The workgroup size is the largest any problem of the group asks for: the
+// WHICH: 0 forward, 1 dQ, 2 dK/dV, 3 the one-pass backward.  The workgroup size is the largest any problem of the group asks for: the
 // surplus waves of a smaller problem stage tiles and then find no tile of their own.
 template <int DQK, int DV, int WHICH>
-__global__ __launch_bounds__(512, (WHICH == 2 && DQK <= 32 && DV <= 32) ? DKV32_MIN_BLOCKS : 1) void attn_grouped_kernel(const AttnGroup g) {
+__global__ __launch_bounds__(512, WHICH == 3 ? 4 : (WHICH == 2 && DQK <= 32 && DV <= 32) ? DKV32_MIN_BLOCKS : 1) void attn_grouped_kernel(const AttnGroup g) {
   int pi = 0;
   while (pi + 1 < g.count && (int)blockIdx.x >= g.first_block[pi + 1]) ++pi;
   int bh = (int)blockIdx.x - g.first_block[pi];
-  if (DQK <= 32 && g.prob[pi].pair && !(g.first_block[pi] & 7)) bh = pair_heads(bh, g.first_block[pi + 1] - g.first_block[pi]);
+  if (WHICH != 3 && DQK <= 32 && g.prob[pi].pair && !(g.first_block[pi] & 7)) bh = pair_heads(bh, g.first_block[pi + 1] - g.first_block[pi]);
   // (a copy in registers: read through a reference into the by-value table, every field the loops use came back as a scalar load
   // + wait per iteration — the "memory" clobbers of the staging waits forbid hoisting them)
   const AttnParams p = g.prob[pi];
   if (WHICH == 0) attn_fwd_body<DQK, DV, false, 1>(p, bh, 0);
   else if (WHICH == 1) attn_bwd_dq_body<DQK, DV, false, bwd_tiles<DQK, DV>()>(p, bh, 0);
-  else attn_bwd_dkv_body<DQK, DV, false, bwd_tiles<DQK, DV>()>(p, bh, 0);
+  else if (WHICH == 2) attn_bwd_dkv_body<DQK, DV, false, bwd_tiles<DQK, DV>()>(p, bh, 0);
+  else if constexpr (WHICH == 3) attn_bwd_one_body<DQK, DV>(p, bh);
 }
 
 template <int DQK> constexpr int padqk() { return DQK < 32 ? 32 : DQK; }      // LDS columns of a q/k (or v/dO) row
@@ -850,10 +1043,28 @@ inline int waves_for_tiles(int rows, int per) {
 template <int DQK, int DV> constexpr size_t attn_row_bytes() { return (size_t)padqk<DQK>() * 2 + (size_t)padqk<DV>() * 2; }
 template <int DQK, int DV, int WHICH> size_t attn_lds(const AttnParams& p) {
   const int Nkp = (p.Nk + 31) & ~31, Nqp = (p.Nq + 31) & ~31;
+  if (WHICH == 3) return Nqp * attn_row_bytes<DQK, DV>() + (size_t)Nkp * padqk<DQK>() * 2 + (size_t)Nqp * Nkp * 2 + Nqp * 8;      // Q, dO, K, the dS^T patch, LSE + Delta
   return WHICH == 2 ? Nqp * (attn_row_bytes<DQK, DV>() + 8) : Nkp * attn_row_bytes<DQK, DV>();
 }
 template <int DQK, int DV, int WHICH> int attn_waves(const AttnParams& p) {
+  if (WHICH == 3) return std::max(waves_for((p.Nk + 31) & ~31), waves_for(p.Nq));      // phase A walks the padded key tiles, phase B the query tiles
   return WHICH == 0 ? waves_for(p.Nq) : waves_for_tiles(WHICH == 2 ? p.Nk : p.Nq, bwd_tiles<DQK, DV>());
+}
+
+// Which backward problems take the one-pass kernel (part 3 of launch_bwd).  Head widths (64, 64) and (16, 64): the towers' and the
+// fusion block's; no bias, no score-gradient output, no dropout.  The whole working set must fit ATTN_RESIDENT_MAX, so that two
+// workgroups share a CU — which is also the upper cut-off: with 64-wide heads that is 2 Nqp Nkp + 264 Nqp + 128 Nkp <= 80 KB (row
+// counts padded to 32), e.g. 64 x 96 (40.5 KB), 96 x 128 (64.8 KB), 128 x 128 (81 KB: no); the decoders' 228 / 352 rows (d = 32)
+// stay on the dQ + dK/dV pair.  Mirrored by ops.attn_bwd_onepass_fits (the engine's choice of one region or two).
+template <int DQK, int DV> constexpr bool onepass_widths() { return (DQK == 64 || DQK == 16) && DV == 64; }
+template <int DQK, int DV> bool onepass_fits(const AttnParams& p) {
+  if (!onepass_widths<DQK, DV>()) return false;
+  if (p.bias || p.dS || p.keep || p.debug || dav_attn_onepass == 1) return false;
+  // Recorded into a LANE of a launch batch (batch.h), a backward keeps its two ranks: the lanes of a batch are walked in lockstep, and
+  // every caller's line-up (lane_skip counts, which GEMMs of the other lanes a rank meets) counts a backward attention as dQ, then
+  // dK/dV.  Direct launches and all-independent batches (regions) have no ranks to keep.  Both paths give the same bits.
+  if (davb::lockstep()) return false;
+  return attn_lds<DQK, DV, 3>(p) <= ATTN_RESIDENT_MAX;
 }
 
 // issues n >= 1 recorded resident-variant problems of one (head widths, pass) family: davb::GroupFn
@@ -875,9 +1086,12 @@ void attn_issue(const void* const* params_in, int n, hipStream_t stream) {
     } else if (WHICH == 1) {
       (void)raise_lds_cap<attn_bwd_dq_kernel<DQK, DV, false>>(lds);
       DAV_LAUNCH_NOW((attn_bwd_dq_kernel<DQK, DV, false>), dim3(p.B * p.H), dim3(nw * 64), lds, stream, p);
-    } else {
+    } else if (WHICH == 2) {
       (void)raise_lds_cap<attn_bwd_dkv_kernel<DQK, DV, false>>(lds);
       DAV_LAUNCH_NOW((attn_bwd_dkv_kernel<DQK, DV, false>), dim3(p.B * p.H), dim3(nw * 64), lds, stream, p);
+    } else if constexpr (WHICH == 3) {
+      (void)raise_lds_cap<attn_bwd_onepass_kernel<DQK, DV>>(lds);
+      DAV_LAUNCH_NOW((attn_bwd_onepass_kernel<DQK, DV>), dim3(p.B * p.H), dim3(nw * 64), lds, stream, p);
     }
   };
   for (int base = 0; base < n; base += ATTN_GROUP_MAX) {
@@ -988,6 +1202,12 @@ int launch_bwd(const AttnParams& p, hipStream_t stream, int part = 3) {
   const size_t row = attn_row_bytes<DQK, DV>();
   const size_t lds1 = attn_lds<DQK, DV, 1>(p), lds2 = attn_lds<DQK, DV, 2>(p);
   const int nw1 = waves_for(p.Nq), nw2 = waves_for(p.Nk);
+  if constexpr (onepass_widths<DQK, DV>()) {
+    if (part == 3 && onepass_fits<DQK, DV>(p)) {
+      attn_resident<DQK, DV, 3>(p, stream);
+      return dav_launch_status();
+    }
+  }
   // dQ first: it also writes Delta, which the dK/dV kernel reads
   if (!(part & 1)) {
   } else if (lds1 <= ATTN_RESIDENT_MAX) {

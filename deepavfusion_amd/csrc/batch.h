@@ -22,6 +22,7 @@ namespace davb {
 typedef void (*GroupFn)(const void* const* params, int n, hipStream_t stream);
 
 bool recording();
+bool lockstep();                                                                // recording into caller-declared LANES (not an all-independent batch)
 void push_opaque(std::function<void()> fn);                                    // any other launch: replayed as is
 void push_typed(GroupFn fn, const void* params, size_t bytes, hipStream_t stream);
 

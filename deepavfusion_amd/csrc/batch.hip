@@ -43,6 +43,7 @@ Step& cur_step() {
 }  // namespace
 
 bool recording() { return S.on && !S.suspended; }
+bool lockstep() { return recording() && !S.auto_lanes; }
 
 void push_opaque(std::function<void()> fn) {
   Op op;

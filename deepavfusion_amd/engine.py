@@ -1186,7 +1186,11 @@ def _factorized_bwd_cross(fb, t, g1, dov, doa, dxmm_b, dx_i, dx_a):
     dq_v, dkv_v = _e((B * nv, D), BF16, dev), _e((B * nI, 2 * D), BF16, dev)
     dq_a, dkv_a = _e((B * na, D), BF16, dev), _e((B * nA, 2 * D), BF16, dev)
     del_v, del_a = torch.empty_like(cv['lse']), torch.empty_like(ca['lse'])
-    for part in (1, 2):      # dQ kernels of both aggregations, then their dK/dV kernels: two steps, like a tower block's attention
+    # one region when both aggregations take the one-pass backward kernel; else — and as a lane of a launch batch, where a backward
+    # attention keeps its two ranks beside the tower blocks' — the dQ kernels of both, then their dK/dV kernels: two steps
+    one = (PRECISION != 'fp32' and (_BATCH is None or _BATCH.auto_lanes)
+           and ops.attn_bwd_onepass_fits(nv, nI, hd, hd) and ops.attn_bwd_onepass_fits(na, nA, hd, hd))
+    for part in ((3,) if one else (1, 2)):
         with region():
             attention_bwd((cv['q'], 0), (cv['kv'], 0), (cv['kv'], D), cv['o'], dov, cv['lse'], (dq_v, 0), (dkv_v, 0), (dkv_v, D),
                           B, heads, nv, nI, hd, hd, hd ** -0.5, nv * D, D, nI * 2 * D, 2 * D, nI * 2 * D, 2 * D,
@@ -1554,6 +1558,7 @@ def _dense_bwd(fb, t, g, gb, *, dx_i=None, dx_a=None):
 # forward: k/v pair projections, pair_expand, pair attention, its proj (steps 5-8) sit between the towers' proj and norm2;
 # backward: pair attention dQ, dK/dV, [q2 dgrad + pair_reduce], k dgrads, v dgrads, aggregation-proj dgrads (steps 5-10)
 FUSION_IDLE_FWD, FUSION_IDLE_BWD = 4, 6
+
 
 
 def fusion_block_batchable(fb, dp=None, dr=None):

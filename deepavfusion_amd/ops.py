@@ -349,6 +349,23 @@ def attn_bwd(q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr, B, 
                                      dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), part, _stream()), 'dav_attn_bwd')
 
 
+ATTN_RESIDENT_MAX = 80 * 1024      # csrc/attention.hip: LDS of a resident attention workgroup (two per CU)
+
+
+def attn_bwd_onepass_lds(Nq, Nk, dqk, dv):
+    """Dynamic LDS bytes of the one-pass attention backward (csrc/attention.hip attn_lds<.., 3>): Q, dO and K tiles with rows padded to
+    32 and head widths to at least 32 columns, the bf16 dS^T patch, LSE + Delta."""
+    nqp, nkp = (Nq + 31) & ~31, (Nk + 31) & ~31
+    return nqp * (2 * max(dqk, 32) + 2 * max(dv, 32)) + nkp * 2 * max(dqk, 32) + nqp * nkp * 2 + nqp * 8
+
+
+def attn_bwd_onepass_fits(Nq, Nk, dqk, dv):
+    """Mirror of onepass_fits (csrc/attention.hip) at the default knob setting: does ``attn_bwd(part=3)`` without bias / dropout go
+    out as ONE launch?  (Not when it is recorded into a lane of a launch batch: there a backward keeps its two ranks.)  The engine
+    chooses one region or two for the aggregations' backward with it; the library decides on its own."""
+    return (dqk, dv) in ((64, 64), (16, 64)) and attn_bwd_onepass_lds(Nq, Nk, dqk, dv) <= ATTN_RESIDENT_MAX
+
+
 def layernorm_fwd(x0, x0_bs, r0, x1, x1_bs, r1, B, D, gamma, beta, eps, y_bf16, y_f32, mean, rstd):
     lib = _lib.load()
     if y_bf16 is not None and y_bf16.dtype == F32:      # fp32 path: the "operand copy" of the output is fp32 too

@@ -43,7 +43,10 @@ int dav_build_flags(void);   /* bit 0: experimental build (make EXPERIMENTAL=1):
 /* text of the last HIP error latched by a kernel launch of the calling thread (diagnostics) */
 const char* dav_last_error_string(void);
 /* launch-geometry knobs for tuning experiments (1: LayerNorm-backward waves per workgroup {2,4,8}; 2: its grid cap;
- * 3: query tiles per wave of the attention forward, 0 = automatic, 1, 2) */
+ * 3: query tiles per wave of the attention forward, 0 = automatic, 1, 2;
+ * 5: the attention backward of short problems, 0 = the fit rule (one launch when the whole (batch, head) problem fits 80 KB of LDS,
+ *    head widths (64, 64) / (16, 64), no bias / dropout, not recorded into a lane of a launch batch), 1 = always the dQ + dK/dV kernel pair, 2 = one pass whenever it fits.
+ * (4 belonged to a probe that is gone.)  An unknown knob or value returns DAV_ERR_SHAPE. */
 int dav_tune(int knob, int value);
 
 /* ---- GEMM --------------------------------------------------------------------------------- */

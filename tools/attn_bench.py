@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times dav_attn_fwd / dav_attn_bwd on the path's shapes (hipGraph replay of `reps` launches).
-Usage: python tools/attn_bench.py [name ...]   names: enc_img enc_aud dec_img dec_aud pair video eval_aud"""
+Usage: python tools/attn_bench.py [name ...]   names: enc_img enc_aud dec_img dec_aud video eval_aud ... (SHAPES)"""
 import os
 import sys
 
@@ -23,6 +23,13 @@ SHAPES = {   # B, H, Nq, Nk, dqk, dv, query row offset in the fused buffer
     'video_aud': (16, 12, 96, 128, 64, 64, 32),
     'eval_aud': (64, 12, 320, 352, 64, 64, 32),
     'long': (4, 12, 4096, 4096, 64, 64, 0),
+    # around the upper end of the one-pass backward's fit rule (csrc/attention.hip onepass_fits; DAV_TUNE=5:1 = the kernel pair)
+    'agg_aud': (64, 12, 8, 63, 64, 64, 55),
+    'm75_aud': (64, 12, 80, 112, 64, 64, 32),
+    'lim_96x128': (64, 12, 96, 128, 64, 64, 32),
+    'lim_64x160': (64, 12, 64, 160, 64, 64, 96),
+    'lim_32x256': (64, 12, 32, 256, 64, 64, 224),
+    'over_128x128': (64, 12, 128, 128, 64, 64, 0),
 }
 
 
