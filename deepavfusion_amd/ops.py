@@ -668,3 +668,31 @@ def knn_topk(queries, banks, k, sum_view=True, splits=None, out=None, workspace=
                                             _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
                'dav_knn_topk_f32')
     return out[0], out[1].long()
+
+
+# ---- frame transform of the input stage (csrc/data/frames.hip) -----------------------------------------------------------
+
+FRAME_PARAM_COLS = 9    # i, j, h, w, RH, RW, top, left, flip (include/dav_kernels.h)
+
+
+def frame_transform(frames, params, size, mean, std, out=None):
+    """Crop + antialiased bilinear resample + flip + /255 + (x - mean) / std of a batch of frames in one launch
+    (dav_frame_transform_u8).  frames uint8 [B, H, W, 3] dense on the device, params int32 [B, 9] on the device (rows as in
+    include/dav_kernels.h; the kernel clamps them, callers validate them on the host before upload: util/frame_transforms.py),
+    mean / std three floats each -> fp32 [B, 3, size, size]."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError('frame_transform needs dense uint8 frames [B, H, W, 3]')
+    B, H, W, _ = frames.shape
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, FRAME_PARAM_COLS) or not params.is_contiguous():
+        raise ValueError(f'frame_transform needs dense int32 params [{B}, {FRAME_PARAM_COLS}]')
+    if params.device != frames.device:
+        raise ValueError('frames and params live on different devices')
+    size = int(size)
+    if out is None:
+        out = torch.empty(B, 3, size, size, dtype=F32, device=frames.device)
+    elif out.dtype != F32 or tuple(out.shape) != (B, 3, size, size) or not out.is_contiguous():
+        raise ValueError(f'frame_transform writes dense fp32 [{B}, 3, {size}, {size}]')
+    m, s = [float(v) for v in mean], [float(v) for v in std]
+    _lib.check(_lib.load().dav_frame_transform_u8(_ptr(frames), B, H, W, _ptr(params), size, m[0], m[1], m[2], s[0], s[1], s[2],
+                                                  _ptr(out), _stream()), 'dav_frame_transform_u8')
+    return out

@@ -14,8 +14,10 @@ Documented differences from the reference:
     order of ties unspecified);
   - the loader order is re-seeded at every call (the same clips, in the same order, at every epoch), and DataLoader workers
     follow ``env.workers`` (the reference forces at least one);
-  - ``dataset=synthetic`` is a labelled synthetic set (seeded class prototypes + seeded noise); VGGSound / AudioSet need PyAV and
-    torchaudio, which are not dependencies of this project.  Python callers may pass any dataset that yields
+  - ``dataset=synthetic`` is a labelled synthetic set (seeded class prototypes + seeded noise); ``dataset=shards`` reads a labelled
+    clip-shard partition (util/clip_shards.py: pre-decoded clips, ``train=False``) and runs the reference's eval transforms on the
+    device (EvalFrameTransform; Pad -> LogMelSpectrogram, no RandomVol).  VGGSound / AudioSet by name need PyAV and torchaudio,
+    which are not dependencies of this project.  Python callers may pass any dataset that yields
     ``(image, spec, {'class': label})`` — the reference's contract; multi-hot labels ([num_classes] per clip) select the AP / AUC
     metrics.
 """
@@ -121,6 +123,7 @@ class EvalAVNNProbe:
         self.print_freq = int(log_args.print_freq)
         self.dataset = probe_args.get('dataset') if dataset is None else 'custom'
         self.seed = int(env_args.get('seed') or 0)
+        self.frame_frontend = self.audio_frontend = None       # shards: raw frames / waveforms in, transforms on the device
         if dataset is not None:
             self.db, self.multi_label = dataset, None          # decided by the label shape
         elif self.dataset == 'synthetic':
@@ -129,9 +132,23 @@ class EvalAVNNProbe:
             self.db = SyntheticLabelledAV(int(probe_args.num_samples), int(probe_args.num_classes), image_size, audio_size,
                                           seed=self.seed)
             self.multi_label = False
+        elif self.dataset == 'shards':
+            from . import audio_transforms as aT
+            from .clip_shards import ClipShards
+            from .frame_transforms import EvalFrameTransform
+            if not probe_args.get('data_path'):
+                raise ValueError('nn_probe.dataset=shards needs nn_probe.data_path (default: data.data_path)')
+            self.db = ClipShards(probe_args.data_path, probe_args.get('partition') or 'test', audio_dur=float(probe_args.audio_dur),
+                                 audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed)
+            if not self.db.has_labels:
+                raise ValueError(f'{self.db.dir} has no labels.npy: the nearest-neighbour probe needs a labelled shard set')
+            self.multi_label = self.db.multi_label
+            self.frame_frontend = EvalFrameTransform(int(probe_args.image_size))
+            self.audio_frontend = aT.Compose([aT.Pad(float(probe_args.audio_dur), int(probe_args.audio_rate)),
+                                              aT.LogMelSpectrogram(int(probe_args.audio_rate), int(probe_args.audio_mels))])
         elif self.dataset in ('vggsound', 'audioset'):
-            raise NotImplementedError(f'nn_probe.dataset={self.dataset}: only nn_probe.dataset=synthetic is on the MI355X path '
-                                      '(the reference datasets need PyAV/torchaudio)')
+            raise NotImplementedError(f'nn_probe.dataset={self.dataset}: synthetic and shards are on the MI355X path '
+                                      '(the reference datasets need PyAV/torchaudio; decode them with tools/make_shards.py)')
         else:
             raise NotImplementedError(f'nn_probe.dataset={self.dataset}')
         if self.distributed:
@@ -158,7 +175,10 @@ class EvalAVNNProbe:
         try:
             for image, spec, anno in self.loader:
                 spec = spec.to(self.device, non_blocking=True).float()
-                image = image.to(self.device, non_blocking=True).float()
+                image = image.to(self.device, non_blocking=True)
+                image = self.frame_frontend(image) if self.frame_frontend is not None else image.float()
+                if self.audio_frontend is not None:
+                    spec = self.audio_frontend(spec)
                 lbl = anno['class'].to(self.device, non_blocking=True).long()
                 for f, x in zip(feats, model.forward_encoder(image, spec)[:3]):      # x_v, x_a, x_mm
                     f.append(ops.mean_l2n(x))

@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 extern "C" {
 #endif
 
-#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) (9 also: dav_mean_l2n_f32, dav_knn_topk_f32) */
+#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) (9 also: dav_mean_l2n_f32, dav_knn_topk_f32, dav_frame_transform_u8) */
 int dav_abi_version(void);
 int dav_build_flags(void);   /* bit 0: experimental build (make EXPERIMENTAL=1): the rejected GEMM tile configurations exist */
 /* text of the last HIP error latched by a kernel launch of the calling thread (diagnostics) */
@@ -364,6 +364,25 @@ int dav_logmel(const float* wave, int B, int S, int n_fft, int hop, int n_mels, 
                const float* sin_tab, const float* fbank, const int* band_lo, const int* band_hi, float eps, int apply_log,
                int drop_last, float* out, hipStream_t stream);
 int dav_log10_eps(const float* x, float eps, long n, float* y, hipStream_t stream);      /* aT.Log: y = log10(x + eps) */
+
+/* ---- frame transform of the input stage (csrc/data/frames.hip) -------------------------------- */
+/* The reference's frame transforms on the device, from uint8 frames instead of PIL images in CPU loader workers:
+ * RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize (train.py:45-49) and Resize -> CenterCrop -> ToTensor ->
+ * Normalize (util/knn_probe.py:31-36).  frames uint8 [B, H, W, 3] (HWC, dense) -> out fp32 [B, 3, S, S] (CHW, dense).
+ * params int32 [B, 9] on the device, per sample: source window (i, j, h, w) = (top row, left column, rows, columns); virtual
+ * output size (RH, RW) the window is resampled to; origin (top, left) of the emitted S x S window inside the virtual output;
+ * flip (non-zero: the emitted window is mirrored left-right).  Resized crop: window = crop box, (RH, RW) = (S, S), origin (0, 0);
+ * resize + centre crop: window = whole frame, (RH, RW) = resized size, origin = crop offset.
+ * Resampling: the antialiased bilinear (triangle) filter of PIL's Image.resize(BILINEAR) / F.interpolate(mode='bilinear',
+ * antialias=True), separable, per axis scale = n_in / n_out, support = max(scale, 1), centre c = (o + 0.5) scale, taps
+ * k in [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), n_in)) INSIDE the window (pixels outside the crop box never
+ * contribute), weight max(0, 1 - |k - c + 0.5| / support) divided by the sum of the weights; the weights are formed exactly
+ * (integers over 2 max(n_in, n_out)), sums in fp32, NO rounding to uint8 between the passes or at the end (PIL does both).
+ * Then out = (v / 255 - mean_c) / std_c.  Every index is clamped into the frame and every parameter into range: a bad row gives
+ * a wrong picture, never an out-of-bounds access.  B <= 65535; H, W, S <= 16384; S a multiple of 16; std_c > 0 (else -1);
+ * out 16-byte, params 4-byte aligned (else -5).  One launch, no workspace. */
+int dav_frame_transform_u8(const uint8_t* frames, int B, int H, int W, const int* params, int S, float mean0, float mean1,
+                           float mean2, float std0, float std1, float std2, float* out, hipStream_t stream);
 
 /* ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------- */
 /* out[b, :] = v / max(||v||_2, 1e-12) with v = mean over l of x[b, l, :]: the x.mean(dim=1) + F.normalize(p=2, dim=1) of

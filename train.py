@@ -8,7 +8,9 @@ non-finite guard -> Trainer.step -> metrics {loss, loss_image, loss_audio, grad_
 
 Hydra/omegaconf are not available in this environment: the YAML files under configs/ (same keys as the
 reference) are composed by a small loader with ``${a.b}`` interpolation and ``a.b=value`` overrides.
-Only ``data.dataset=synthetic`` is implemented (tensor contract of SURVEY.md section 2 row 19)."""
+``data.dataset=synthetic`` (the default; tensor contract of SURVEY.md section 2 row 19) trains on seeded noise;
+``data.dataset=shards data.data_path=DIR`` trains on pre-decoded clips (deepavfusion_amd/util/clip_shards.py, tools/make_shards.py):
+the loader ships uint8 frames and raw waveforms, the reference's frame and audio transforms run on the device."""
 import math
 import os
 import re
@@ -112,11 +114,25 @@ def main_worker(local_rank, args):
 
     image_size = (args.data.image_size, args.data.image_size)
     audio_size = (args.data.audio_mels, int(args.data.audio_dur * 64))  # train.py:65
-    if args.data.dataset != 'synthetic':
-        raise NotImplementedError('only data.dataset=synthetic is on the MI355X path (the reference datasets need PyAV/torchaudio)')
-    gpu_frontend = args.data.get('audio_frontend', 'loader') == 'gpu'     # waveforms in, log-mel computed on the device
-    dataset = SyntheticAV(args.data.steps_per_epoch * eff_batch_size, image_size, audio_size, seed=args.env.seed or 0,
-                          wave_samples=int(args.data.audio_dur * args.data.audio_rate) if gpu_frontend else 0)
+    if args.data.dataset not in ('synthetic', 'shards'):
+        raise NotImplementedError(f'data.dataset={args.data.dataset}: synthetic and shards are on the MI355X path (the reference '
+                                  'datasets need PyAV/torchaudio; decode them into clip shards with tools/make_shards.py)')
+    shards = args.data.dataset == 'shards'
+    gpu_frontend = args.data.get('audio_frontend', 'auto') == 'gpu' or shards     # waveforms in, log-mel computed on the device
+    if shards:
+        from deepavfusion_amd.util.clip_shards import ClipShards
+        if args.data.get('audio_frontend', 'auto') == 'loader':
+            raise ValueError('data.dataset=shards yields raw uint8 frames and waveforms: its transforms run on the device; '
+                             'data.audio_frontend=loader (log-mel made by the loader) does not exist for it — leave it at auto or gpu')
+        if not args.data.get('data_path'):
+            raise ValueError('data.dataset=shards needs data.data_path=<folder holding <partition>/meta.json>')
+        dataset = ClipShards(args.data.data_path, args.data.get('partition') or 'train', audio_dur=args.data.audio_dur,
+                             audio_rate=args.data.audio_rate, train=True, seed=args.env.seed or 0)
+        if len(dataset) < eff_batch_size:
+            raise ValueError(f'{dataset.dir}: {len(dataset)} clips are fewer than one global batch of {eff_batch_size}')
+    else:
+        dataset = SyntheticAV(args.data.steps_per_epoch * eff_batch_size, image_size, audio_size, seed=args.env.seed or 0,
+                              wave_samples=int(args.data.audio_dur * args.data.audio_rate) if gpu_frontend else 0)
     sampler = torch.utils.data.DistributedSampler(dataset, shuffle=True) if num_tasks > 1 else torch.utils.data.RandomSampler(dataset)
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.opt.batch_size, sampler=sampler, num_workers=args.env.workers,
                                          pin_memory=True, drop_last=True)
@@ -154,15 +170,23 @@ def main_worker(local_rank, args):
         from deepavfusion_amd.util.knn_probe import EvalAVNNProbe
         knn_probe = EvalAVNNProbe(args.nn_probe, args.log, args.env)
 
-    frontend = None
+    frontend = frame_frontend = None
     if gpu_frontend:
         from deepavfusion_amd.util.audio_transforms import LogMelSpectrogram
         frontend = LogMelSpectrogram(sample_rate=args.data.audio_rate, n_mels=args.data.audio_mels).to(device)
+    if shards:                                                       # train.py:45-54 of the reference, on the device
+        from deepavfusion_amd.util import audio_transforms as aT
+        from deepavfusion_amd.util.frame_transforms import TrainFrameTransform
+        frame_frontend = TrainFrameTransform(args.data.image_size, scale=(args.data.crop_min, 1.))
+        frontend = aT.Compose([aT.Pad(args.data.audio_dur, args.data.audio_rate), aT.RandomVol(per_sample=True), frontend])
     print(f'Start training for {args.opt.epochs} epochs')
     for epoch in range(start_epoch, args.opt.epochs):
         if num_tasks > 1:
             loader.sampler.set_epoch(epoch)
-        train_one_epoch(loader, trainer, epoch, device, args, graphed, frontend)
+        if shards:                                                   # the draws of an epoch follow (seed, epoch[, rank]): a resumed run repeats them
+            dataset.set_epoch(epoch)
+            frame_frontend.seed(((args.env.seed or 0) * 1_000_003 + epoch) * 1024 + dist_utils.get_rank())
+        train_one_epoch(loader, trainer, epoch, device, args, graphed, frontend, frame_frontend)
         if graphed is not None:
             graphed.check()          # never write a checkpoint behind a skipped (non-finite) captured step: raise like train.py:166-167
         if knn_probe is not None and (epoch % args.log.eval_freq == 0 or epoch == args.opt.epochs - 1 or epoch == start_epoch):
@@ -171,7 +195,7 @@ def main_worker(local_rank, args):
         ckpt.checkpoint(epoch + 1, {'epoch': epoch + 1})
 
 
-def train_one_epoch(loader, trainer, epoch, device, args, graphed=None, frontend=None):
+def train_one_epoch(loader, trainer, epoch, device, args, graphed=None, frontend=None, frame_frontend=None):
     from deepavfusion_amd.util import lr_sched
     trainer.model.train(True)
     trainer.zero_grad()
@@ -179,7 +203,8 @@ def train_one_epoch(loader, trainer, epoch, device, args, graphed=None, frontend
     for step, (image, audio, _) in enumerate(loader):
         if step % args.opt.accum_iter == 0:
             lr = lr_sched.adjust_learning_rate(trainer.optimizer, epoch + step / len(loader), args)
-        image = image.to(device, non_blocking=True).float()
+        image = image.to(device, non_blocking=True)
+        image = frame_frontend(image) if frame_frontend is not None else image.float()     # uint8 [B, H, W, 3] -> [B, 3, size, size]
         audio = audio.to(device, non_blocking=True).float()
         if frontend is not None:
             audio = frontend(audio)                 # [B, samples] -> [B, 1, n_mels, 64 * dur] on the device
