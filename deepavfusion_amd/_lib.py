@@ -39,6 +39,8 @@ SIGNATURES = {
     'dav_gemm_tn_grouped_bf16': [_p, _i, _p],
     'dav_gemm_tn_gang_workspace_bytes': [_p, _i],
     'dav_gemm_tn_gang_bf16': [_p, _i, _p, _sz, _p],
+    'dav_gemm_tn_grouped_bf16_gated': [_p, _i, _p, _p],
+    'dav_gemm_tn_gang_bf16_gated': [_p, _i, _p, _sz, _p, _p],
     'dav_attn_fwd': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _i, _l, _i, _l, _i, _l, _i, _f, _p],
     'dav_attn_bwd': [_p] * 10 + [_i] * 6 + [_l, _i] * 8 + [_f, _p],
     'dav_attn_bwd_part': [_p] * 10 + [_i] * 6 + [_l, _i] * 8 + [_f, _i, _p],

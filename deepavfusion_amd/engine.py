@@ -531,9 +531,12 @@ class deferred_wgrads:
 _OVERWRITE = None          # None: off;  dict(written=set of C addresses, touched=set of C addresses, params=set of id(weight))
 
 
-def wgrad_overwrite_begin():
+def wgrad_overwrite_begin(gate=None):
+    """``gate`` (int32 [1] on the device; a captured gradient-accumulation window): the written first contributions go out through
+    the GATED launches — written while gate[0] != 0 at replay time (the window's first micro-step), accumulated otherwise.  A
+    problem whose launch has no gated form (the one-problem kernel, the fp32 path) then stays on accumulate / zero-fill."""
     global _OVERWRITE
-    _OVERWRITE = dict(written=set(), touched=set(), params={})
+    _OVERWRITE = dict(written=set(), touched=set(), params={}, gate=gate)
 
 
 def wgrad_overwrite_end():
@@ -581,22 +584,28 @@ def flush_wgrads():
         # longest contractions first: tiles are dispatched in list order as workgroup slots free up, and a tile's run time is
         # proportional to its contraction length (49 .. 95 k-steps in one launch) — the short ones fill the tail
         now.sort(key=lambda pr: -pr['Mc'])
+        gate = _OVERWRITE['gate'] if _OVERWRITE is not None else None
+        gated = {} if gate is None else {'gate': gate}          # (no gate: today's calls, argument for argument)
+        gang = WGRAD_GANG and PRECISION == 'bf16' and (sum(-(-pr['N'] // 256) * -(-pr['K'] // 256) for pr in now) >= WGRAD_GANG_MIN_TILES
+                                                       or any(pr['Mc'] % 64 for pr in now))      # (a ragged contraction has no other fast kernel)
         if _OVERWRITE is not None:
             for pr in now:
                 key = pr['C'].data_ptr()
                 pr['overwrite'] = bool(pr.get('weight') is not None and key not in _OVERWRITE['written'] and key not in _OVERWRITE['touched'])
+                if gate is not None and (pr['A'].dtype == F32 or (not gang and pr['Mc'] % 64)):      # its launch has no gated form
+                    pr['overwrite'] = False
                 _OVERWRITE['written'].add(key)
                 if pr.get('weight') is None:                       # a column block: the weight as a whole stays on accumulate / zero-fill
                     _OVERWRITE['touched'].add(pr.get('gbase', key))
                 if pr['overwrite']:
                     _OVERWRITE['params'][id(pr['weight'])] = pr['weight']
-        if WGRAD_GANG and PRECISION == 'bf16' and (sum(-(-pr['N'] // 256) * -(-pr['K'] // 256) for pr in now) >= WGRAD_GANG_MIN_TILES
-                                                   or any(pr['Mc'] % 64 for pr in now)):      # (a ragged contraction has no other fast kernel)
-            ops.gemm_tn_gang(now)          # one persistent launch of 256 x 256 tiles, gangs of panel-sharing tiles per XCD
+        if gang:
+            # one persistent launch of 256 x 256 tiles, gangs of panel-sharing tiles per XCD
+            ops.gemm_tn_gang(now, **gated)
         else:
             grouped = [pr for pr in now if pr['Mc'] % 64 == 0 or pr['A'].dtype == F32]
             if grouped:
-                ops.gemm_tn_grouped(grouped)
+                ops.gemm_tn_grouped(grouped, **gated)
             for pr in now:                 # (a ragged contraction in a flush too small for the gang launch: the one-problem kernel)
                 if pr['Mc'] % 64 and pr['A'].dtype != F32:
                     ops.gemm_tn(pr['A'], pr['B'], pr['Mc'], pr['N'], pr['K'], pr['C'], lda=pr['lda'], ldb=pr['ldb'], ldc=pr['ldc'],

@@ -224,11 +224,21 @@ def gemm_tn(A, B, Mc, N, K, C_out, *, lda=None, ldb=None, ldc=None, a_rowmap=Non
 TN_GROUP_MAX = 40          # dav_gemm_tn_grouped_bf16: problems per launch
 
 
-def gemm_tn_grouped(problems):
+def _gate_ptr(gate):
+    if gate.dtype != torch.int32 or gate.numel() != 1 or not gate.is_cuda:
+        raise ValueError('write gate: one int32 element in device memory')
+    return _ptr(gate)
+
+
+def gemm_tn_grouped(problems, gate=None):
     """problems: list of dicts(A, B, Mc, N, K, C, lda, ldb, ldc, a_rowmap, b_rowmap, bias_grad[, overwrite]); see
-    dav_gemm_tn_grouped_bf16 (overwrite: C is written instead of accumulated, DavTnProblem.flags bit 0)."""
+    dav_gemm_tn_grouped_bf16 (overwrite: C is written instead of accumulated, DavTnProblem.flags bit 0).  ``gate`` (int32 [1] on the
+    device): the ``overwrite`` problems are written only while gate[0] != 0 when the launch RUNS, else accumulated
+    (dav_gemm_tn_grouped_bf16_gated; bf16 operands only)."""
     lib = _lib.load()
     if problems and problems[0]['A'].dtype == F32:      # fp32 path: one launch per problem
+        if gate is not None and any(d.get('overwrite') for d in problems):
+            raise RuntimeError('gemm_tn_grouped: the fp32 path has no gated form; queue its problems without overwrite')
         for d in problems:
             gemm_tn(d['A'], d['B'], d['Mc'], d['N'], d['K'], d['C'], lda=d['lda'], ldb=d['ldb'], ldc=d['ldc'],
                     a_rowmap=d.get('a_rowmap'), b_rowmap=d.get('b_rowmap'), beta=0 if d.get('overwrite') else 1,
@@ -240,6 +250,10 @@ def gemm_tn_grouped(problems):
     n_launch = (len(problems) + TN_GROUP_MAX - 1) // TN_GROUP_MAX
     for i in range(n_launch):
         chunk = problems[i::n_launch]
+        if gate is not None:
+            _lib.check(lib.dav_gemm_tn_grouped_bf16_gated(_tn_problem_array(chunk), len(chunk), _gate_ptr(gate), _stream()),
+                       'dav_gemm_tn_grouped_bf16_gated')
+            continue
         _lib.check(lib.dav_gemm_tn_grouped_bf16(_tn_problem_array(chunk), len(chunk), _stream()), 'dav_gemm_tn_grouped_bf16')
 
 
@@ -254,14 +268,15 @@ def _tn_problem_array(problems):
     return arr
 
 
-def gemm_tn_gang(problems, workspace_fill=None):
+def gemm_tn_gang(problems, workspace_fill=None, gate=None):
     """The queued weight-gradient problems of several layers (dicts as for gemm_tn_grouped, no two with the same C) as ONE
     gang-scheduled launch of 256 x 256 tiles (dav_gemm_tn_gang_bf16).  The workspace is allocated here on the current stream
-    (``workspace_fill``: a byte value to fill it with first — tests check that the kernel initialises its own state)."""
+    (``workspace_fill``: a byte value to fill it with first — tests check that the kernel initialises its own state).
+    ``gate``: as for gemm_tn_grouped (dav_gemm_tn_gang_bf16_gated)."""
     if not problems:
         return
     if problems[0]['A'].dtype == F32:
-        return gemm_tn_grouped(problems)
+        return gemm_tn_grouped(problems) if gate is None else gemm_tn_grouped(problems, gate)
     lib = _lib.load()
     arr = _tn_problem_array(problems)
     nbytes = int(lib.dav_gemm_tn_gang_workspace_bytes(arr, len(problems)))
@@ -271,6 +286,9 @@ def gemm_tn_gang(problems, workspace_fill=None):
     if workspace_fill is not None:
         ws.fill_(workspace_fill)
     hold(ws)
+    if gate is not None:
+        _lib.check(lib.dav_gemm_tn_gang_bf16_gated(arr, len(problems), _ptr(ws), nbytes, _gate_ptr(gate), _stream()), 'dav_gemm_tn_gang_bf16_gated')
+        return
     _lib.check(lib.dav_gemm_tn_gang_bf16(arr, len(problems), _ptr(ws), nbytes, _stream()), 'dav_gemm_tn_gang_bf16')
 
 

@@ -169,6 +169,19 @@ def segment_cuts(depth: int, segments: int):
     return sorted({depth} | ({round(depth * ((enc_parts - s) / enc_parts) ** 2) for s in range(1, enc_parts)} - {0, depth}), reverse=True)
 
 
+def micro_step_plan(accums: int, accum_iter: int, dist_active: bool):
+    """What micro-step ``accums`` (0-based position in its window) of ``accum_iter`` does in the captured step (pure function:
+    tested on CPU) -> (write_first, reduce, optimize).  ``write_first``: the gate of the written-first weight gradients is open —
+    only the window's first micro-step may ignore what lies in the gradient buffer; ``reduce``: the micro-step runs the reducer's
+    bucket schedule — only the window's last one, the others are under the ``no_sync`` of util/misc.py:144-148; ``optimize``: grad
+    norm + AdamW follow.  The answer is the same with and without a data-parallel group (``dist_active``): without one the reducer's
+    calls issue no collective and ``__call__`` leaves them out."""
+    if accum_iter < 1 or not 0 <= accums < accum_iter:
+        raise ValueError(f'micro-step {accums} of a window of {accum_iter}')
+    last = accums == accum_iter - 1
+    return accums == 0, last, last
+
+
 class GraphedStep:
     """One pre-training step (forward -> backward -> grad norm -> AdamW) captured in hipGraphs and replayed per
     iteration: ~1900 kernel launches become a handful of graph launches.
@@ -182,14 +195,27 @@ class GraphedStep:
     Non-finite guard: a replay whose loss (or clipped norm) is not finite leaves parameters / moments untouched ON THE DEVICE, but
     the host-side counters still advance for it (``n_steps``, Adam's step count and bias corrections in ``prepare_step``): a run
     is NOT meant to continue past such a step — ``check()`` raises (train.py calls it every print_freq steps, at the end of every
-    epoch and before every checkpoint), exactly where the reference raises on the step itself (train.py:166-167)."""
+    epoch and before every checkpoint), exactly where the reference raises on the step itself (train.py:166-167).
 
-    def __init__(self, trainer: Trainer, image_shape, audio_shape, warmup: int = 2, segments: int = 0, clip_grad=None):
+    Gradient accumulation (``trainer.accum_iter`` > 1; util/misc.py:96-136): the forward/backward is captured ONCE and replayed per
+    micro-batch, grad norm + AdamW are a graph of their own replayed behind the window's last micro-step.  ``trainer.accums`` is the
+    window's counter (shared with the eager ``Trainer.step``, which may take any micro-step of a window).  What differs between
+    the micro-steps is data on the device: the written-first weight gradients go through the gated launches
+    (``engine.wgrad_overwrite_begin(gate)``) and ``self.gate`` is set to ``accums == 0`` in front of every micro-step's replays.
+    The two losses are summed over the window on the device and the guard looks at the sums (a NaN or an infinity survives a sum):
+    one bad micro-step skips the window's update.  ``__call__`` returns the CURRENT micro-batch's losses and the grad norm of the
+    last COMPLETED window (0 before the first) — the window's own norm, sqrt(sum g^2) / accum_iter, on its last micro-step."""
+
+    def __init__(self, trainer: Trainer, image_shape, audio_shape, warmup: int = 2, segments: int = 0, clip_grad=None,
+                 inject_noise: bool = False):
         """``clip_grad``: max global gradient norm (``opt.clip_grad``; util/misc.py:118-120) — the norm is then taken in a
         pass of its own in front of AdamW and the factor min(1, clip / (norm + 1e-6)) reaches the update as a device scalar.
         Always on: the non-finite guard of train.py:166-167 — a step whose loss (or, with clipping, gradient norm) is not
-        finite leaves parameters and moments untouched; ``check()`` raises on the host when it is convenient to look."""
-        assert trainer.accum_iter == 1 and isinstance(trainer.optimizer, FlatAdamW)
+        finite leaves parameters and moments untouched; ``check()`` raises on the host when it is convenient to look.
+        ``inject_noise`` (tests): the masking noise is read from ``self.noise_image`` / ``self.noise_audio``, which
+        ``__call__(..., noise_image=, noise_audio=)`` fills, instead of being drawn inside the graph."""
+        assert trainer.accum_iter >= 1 and isinstance(trainer.optimizer, FlatAdamW)
+        self.accum_iter = int(trainer.accum_iter)
         self.clip_grad = float(clip_grad) if clip_grad else None
         from .. import autograd_bridge as bridge
         self.bridge = bridge
@@ -199,6 +225,11 @@ class GraphedStep:
         dev = self.opt.flat.flat_p.device
         self.image = torch.zeros(image_shape, device=dev)
         self.audio = torch.zeros(audio_shape, device=dev)
+        self.inject_noise = bool(inject_noise)
+        if self.inject_noise:
+            B = image_shape[0]
+            self.noise_image = torch.zeros(B, self.model.image_gs[0] * self.model.image_gs[1], device=dev)
+            self.noise_audio = torch.zeros(B, self.model.audio_gs[0] * self.model.audio_gs[1], device=dev)
         self.world = dist_utils.get_world_size()
         self.reducer = trainer.model.reducer if trainer.distributed else None
         self.dist_active = self.world > 1 or (self.reducer is not None and self.reducer.force)
@@ -257,21 +288,39 @@ class GraphedStep:
         self.bad_steps = torch.zeros(1, dtype=torch.int32, device=dev)
         self._presq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._presq_ws = torch.zeros(1024, dtype=torch.float32, device=dev)
+        # accumulation only: the device flag the gated weight-gradient launches read, the window's loss sums, the last window's norm
+        accum = self.accum_iter > 1
+        self.gate = torch.ones(1, dtype=torch.int32, device=dev) if accum else None
+        self._sums_dirty = False      # a micro-step added to the loss sums and no captured optimizer pass has cleared them since
+        if accum:
+            self.loss_sum_image = torch.zeros((), dtype=torch.float32, device=dev)
+            self.loss_sum_audio = torch.zeros((), dtype=torch.float32, device=dev)
+            self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        gscale = 1.0 / self.accum_iter
 
         def optimizer_pass():
             gnorm = None
             if self.clip_grad is not None:       # the clip factor needs the norm BEFORE the update: one extra read of the gradients
                 ops.l2norm(self.opt.flat.flat_g, self._presq, self._presq_ws, 1.0)
                 gnorm = self._presq
-            ops.step_guard(self.loss_image, self.loss_audio, gnorm, self.clip_grad, 1.0, self.step_scale, self.bad_steps)
-            self.opt.launch_step(fused_norm_and_zero=True, keep_grad=self.keep_grad, gscale_dev=self.step_scale)      # AdamW + sum(g^2) + zero_grad in one pass
-            self.grad_norm = self.opt.sumsq.sqrt()
+            if not accum:
+                ops.step_guard(self.loss_image, self.loss_audio, gnorm, self.clip_grad, 1.0, self.step_scale, self.bad_steps)
+                self.opt.launch_step(fused_norm_and_zero=True, keep_grad=self.keep_grad, gscale_dev=self.step_scale)      # AdamW + sum(g^2) + zero_grad in one pass
+                self.grad_norm = self.opt.sumsq.sqrt()
+                return
+            # the buffer holds the SUM of the window's gradients: the update takes their mean (util/misc.py:96-136), the clip compares
+            # the mean's norm, and the norm reported is the mean's (the reference's norm / accums on the last micro-step)
+            ops.step_guard(self.loss_sum_image, self.loss_sum_audio, gnorm, self.clip_grad, gscale, self.step_scale, self.bad_steps)
+            self.opt.launch_step(grad_scale=gscale, fused_norm_and_zero=True, keep_grad=self.keep_grad, gscale_dev=self.step_scale)
+            torch.mul(self.opt.sumsq.sqrt(), gscale, out=self.grad_norm)
+            self.loss_sum_image.zero_()
+            self.loss_sum_audio.zero_()
         kept = set()
         with torch.cuda.stream(cap):
             self.graphs[0].capture_begin(capture_error_mode=CAPTURE_MODE)
             try:
                 if os.environ.get('DAV_WGRAD_OVERWRITE', '1') != '0':
-                    engine.wgrad_overwrite_begin()       # first weight-gradient GEMM into a Linear weight writes its tile (see engine)
+                    engine.wgrad_overwrite_begin(self.gate)       # first weight-gradient GEMM into a Linear weight writes its tile (see engine)
                 # the encoder layers' weight gradients are merged into one launch per captured segment: they must be out where a
                 # segment ends
                 engine.WGRAD_FLUSH_LAYERS = set(self.cuts)
@@ -280,16 +329,19 @@ class GraphedStep:
                 engine.invalidate_weight_cache(self.model.parameters())
                 engine.refresh_weight_cache(self.model)
                 self.loss_image, self.loss_audio = self._fwd_bwd(layer_cb)
+                if accum:
+                    self.loss_sum_image.add_(self.loss_image.reshape(()))
+                    self.loss_sum_audio.add_(self.loss_audio.reshape(()))
             finally:
                 # (also on an exception: a write-first mode left on would make later EAGER backwards overwrite instead of
                 # accumulate the first contribution to every Linear weight's gradient)
                 kept = {id(p) for p in engine.wgrad_overwrite_end()}
                 engine.WGRAD_FLUSH_LAYERS = None
-            if not self.dist_active:
+            if not self.dist_active and not accum:
                 optimizer_pass()
             self.graphs[seg[0]].capture_end()
             self.opt_graph = None
-            if self.dist_active:
+            if self.dist_active or accum:
                 self.opt_graph = torch.cuda.CUDAGraph()
                 self.opt_graph.capture_begin(pool=self.graphs[0].pool(), capture_error_mode=CAPTURE_MODE)
                 optimizer_pass()
@@ -317,29 +369,67 @@ class GraphedStep:
         """Forward + hand-written backward straight on the engine (no autograd), unit upstream gradients."""
         B, dev = self.image.shape[0], self.image.device
         Li, La = self.model.image_gs[0] * self.model.image_gs[1], self.model.audio_gs[0] * self.model.audio_gs[1]
-        noise_i, noise_a = torch.rand(B, Li, device=dev), torch.rand(B, La, device=dev)
+        if self.inject_noise:
+            noise_i, noise_a = self.noise_image, self.noise_audio
+        else:
+            noise_i, noise_a = torch.rand(B, Li, device=dev), torch.rand(B, La, device=dev)
         with engine.ln_fuse_for(True):
             outs, tape, aux = self.bridge.avmae_fwd(self.model, self.image, self.audio, noise_i, noise_a)
         one = torch.ones((), device=dev)
         self.bridge.avmae_bwd(self.model, tape, one, one, layer_cb=layer_cb)
         return outs[0], outs[1]
 
-    def __call__(self, image, audio):
+    def __call__(self, image, audio, noise_image=None, noise_audio=None):
         self.image.copy_(image, non_blocking=True)
         self.audio.copy_(audio, non_blocking=True)
-        self.opt.prepare_step()
+        if self.inject_noise:
+            self.noise_image.copy_(noise_image, non_blocking=True)
+            self.noise_audio.copy_(noise_audio, non_blocking=True)
+        elif noise_image is not None or noise_audio is not None:
+            raise ValueError('masking noise given to a step captured with inject_noise=False (it draws its own inside the graph)')
+        if self.accum_iter == 1:
+            self.opt.prepare_step()
+            if self.reducer is not None:
+                self.reducer.begin_backward()
+            for s, g in enumerate(self.graphs):
+                g.replay()
+                if self.reducer is not None and self.dist_active:
+                    self.reducer.launch_buckets(self.bucket_sched[s])      # overlaps the next segment's replay
+            if self.opt_graph is not None:
+                self.reducer.finish()
+                self.opt_graph.replay()
+            self.opt.flat.stale = self.kept_params > 0
+            engine.bump_fold_generation()          # the replayed optimizer pass moved the masters: gamma-folded weight copies are re-made on next eager use
+            self.tr.n_steps += 1
+            return self.loss_image, self.loss_audio, self.grad_norm
+        tr = self.tr
+        write_first, reduce, optimize = micro_step_plan(tr.accums, self.accum_iter, self.dist_active)
+        if write_first and self._sums_dirty:       # the window before this one was cut short (Trainer.zero_grad) or closed by an eager step
+            self.loss_sum_image.zero_()
+            self.loss_sum_audio.zero_()
+        # the value travels with the launch (a fill kernel's argument): the host may be many replays ahead of the device, a reused
+        # staging buffer would be rewritten before its copy has run (see FlatAdamW.prepare_step)
+        self.gate.fill_(1 if write_first else 0)
+        reduce = reduce and self.dist_active
         if self.reducer is not None:
-            self.reducer.begin_backward()
+            with contextlib.nullcontext() if reduce or not self.dist_active else tr.model.no_sync():      # earlier micro-steps launch no buckets
+                self.reducer.begin_backward()
         for s, g in enumerate(self.graphs):
             g.replay()
-            if self.reducer is not None and self.dist_active:
+            if reduce:
                 self.reducer.launch_buckets(self.bucket_sched[s])      # overlaps the next segment's replay
-        if self.opt_graph is not None:
-            self.reducer.finish()
-            self.opt_graph.replay()
+        tr.accums += 1
+        self._sums_dirty = True
         self.opt.flat.stale = self.kept_params > 0
-        engine.bump_fold_generation()          # the replayed optimizer pass moved the masters: gamma-folded weight copies are re-made on next eager use
-        self.tr.n_steps += 1
+        if optimize:
+            self.opt.prepare_step()
+            if reduce:
+                self.reducer.finish()
+            self.opt_graph.replay()
+            self._sums_dirty = False
+            engine.bump_fold_generation()          # the replayed optimizer pass moved the masters: gamma-folded weight copies are re-made on next eager use
+            tr.accums = 0
+            tr.n_steps += 1
         return self.loss_image, self.loss_audio, self.grad_norm
 
 

@@ -138,6 +138,15 @@ int dav_gemm_tn_grouped_bf16(const DavTnProblem* problems, int count, hipStream_
 size_t dav_gemm_tn_gang_workspace_bytes(const DavTnProblem* problems, int count);
 int dav_gemm_tn_gang_bf16(const DavTnProblem* problems, int count, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* The two launches above with flags bit 0 decided ON THE DEVICE when the launch runs: a flagged problem is written while
+ * write_gate[0] != 0 and accumulated while it is 0 (an unflagged one is accumulated either way) — one captured launch serves every
+ * micro-step of a gradient-accumulation window (util/misc.py:96-136, accum_iter > 1), the gate open on the first only.  write_gate:
+ * one int32 in device memory, read on `stream` when the launch runs; NULL: DAV_ERR_SHAPE.  Plans, splits (a flagged problem is never
+ * split), workspace size and every other error code as for the ungated entry points. */
+int dav_gemm_tn_grouped_bf16_gated(const DavTnProblem* problems, int count, const int* write_gate, hipStream_t stream);
+int dav_gemm_tn_gang_bf16_gated(const DavTnProblem* problems, int count, void* workspace, size_t workspace_bytes, const int* write_gate,
+                                hipStream_t stream);
+
 /* ---- attention ---------------------------------------------------------------------------- */
 /* softmax(scale * Q K^T) V per (batch, head); element (b, n, h, d) of X is X[b*x_bs + n*x_rs + h*dX + d].
  * (dqk, dv) in {(64,64), (32,32), (16,64)}.  Replaces F.scaled_dot_product_attention inside timm

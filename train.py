@@ -161,9 +161,11 @@ def main_worker(local_rank, args):
                                         save_freq=args.log.save_freq)
     start_epoch = ckpt.resume()[0] if args.opt.resume else 0
     graphed = None
-    if args.opt.get('graph', False) and args.opt.accum_iter == 1:
+    if args.opt.get('graph', False):
         B = args.opt.batch_size
         graphed = misc_utils.GraphedStep(trainer, (B, 3, *image_size), (B, 1, *audio_size), clip_grad=args.opt.clip_grad)
+        print(f'captured step: accum_iter={args.opt.accum_iter}' + (' (one forward/backward graph replayed per micro-batch, the optimizer '
+              'pass once per window)' if args.opt.accum_iter > 1 else ''))
 
     knn_probe = None
     if args.get('nn_probe') and args.nn_probe.get('dataset'):          # train.py:116-117 (nn_probe.dataset=null: no probe)
