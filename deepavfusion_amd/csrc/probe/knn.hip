@@ -8,27 +8,9 @@
 #include "common.h"
 #include "dav_kernels.h"
 
-#define KNN_BQ 128         // queries per workgroup
-#define KNN_BN 128         // bank rows per tile
-#define KNN_BK 16          // d-slice through LDS
-#define KNN_LDK 20         // padded LDS row of a d-slice (floats): ds_read_b128 of 16 rows x 4 groups without bank conflicts
-#define KNN_LDS 130        // padded LDS row of the score tile
+#include "knn_tile.h"      // the 128 x 128 score tile, KnnEntry / KnnArgs, knn_better: shared with knn_wide.hip
 
 namespace {
-
-struct KnnEntry { float v; int i; };
-
-struct KnnArgs {
-  const float* q[3];
-  const float* x[3];
-  long ldq, ldx;
-  int M, Nq, N, D, V, k, tiles_per_split;
-  KnnEntry* ws;
-};
-
-// strict total order: higher score first, ties to the lower bank index — the top-k set is then unique, whatever order the
-// candidates arrive in, so the result does not depend on the bank split or on the query chunking
-__device__ __forceinline__ bool knn_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
 
 // insert (v, i) into the sorted list by a predicated swap chain (no dynamic register indexing); the last entry falls off
 template <int KP>
@@ -82,15 +64,12 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnArgs p) {
   __shared__ __attribute__((aligned(16))) float sA[KNN_BQ * KNN_LDK];
   __shared__ __attribute__((aligned(16))) float sB[KNN_BN * KNN_LDK];
   __shared__ __attribute__((aligned(16))) float sc[KNN_BQ * KNN_LDS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wq = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int g = lane >> 4, rr = lane & 15;
+  const int tid = threadIdx.x;
   const int q0 = blockIdx.x * KNN_BQ;
   const int ntiles = (p.N + KNN_BN - 1) / KNN_BN;
   const int t0 = blockIdx.y * p.tiles_per_split;
   const int t1 = min(t0 + p.tiles_per_split, ntiles);
   const int r = tid >> 1, h = tid & 1;
-  const int D = p.D;
 
   float lv[4][KP];
   int li[4][KP];
@@ -105,75 +84,19 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnArgs p) {
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
       if (m >= p.M) break;
-      const float* __restrict__ Q = p.q[m];
-      const float* __restrict__ X = p.x[m];
       f32x4 acc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // thread loads 2 float4 of each operand per slice: element e = tid + 256 u -> row e / 4, columns 4 (e % 4) .. + 3
-      f32x4 ra[2], rb[2];
-      auto load = [&](int d0) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int e = tid + 256 * u, row = e >> 2, c = d0 + (e & 3) * 4;
-          const int qr = q0 + row, nr = n0 + row;
-          ra[u] = (qr < p.Nq && c < D) ? *(const f32x4*)(Q + (long)qr * p.ldq + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-          rb[u] = (nr < p.N && c < D) ? *(const f32x4*)(X + (long)nr * p.ldx + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      };
-      load(0);
-      for (int d0 = 0; d0 < D; d0 += KNN_BK) {
-        __syncthreads();                        // every wave is done with the previous slice (and the previous view's scan)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int e = tid + 256 * u, row = e >> 2, c = (e & 3) * 4;
-          *(f32x4*)&sA[row * KNN_LDK + c] = ra[u];
-          *(f32x4*)&sB[row * KNN_LDK + c] = rb[u];
-        }
-        __syncthreads();
-        if (d0 + KNN_BK < D) load(d0 + KNN_BK);
-        // lane (rr, g) holds d = d0 + 4 g + s of its row in element s: step s feeds k-slot g with that d, so every score is the
-        // fp32 FMA chain over d in the fixed order (d0, s, g) — the same for every tile, split and query chunking
-        f32x4 fa[4], fb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i] = *(const f32x4*)&sA[(wq + 16 * i + rr) * KNN_LDK + 4 * g];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = *(const f32x4*)&sB[(wn + 16 * j + rr) * KNN_LDK + 4 * g];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][s], fb[j][s], acc[i][j], 0, 0, 0);
-      }
+      knn_score_tile(p, p.q[m], p.x[m], q0, n0, sA, sB, acc);
       if (p.V > p.M) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j) sum[i][j] = m == 0 ? acc[i][j] : sum[i][j] + acc[i][j];
       }
-      // view m: C/D layout col = lane & 15 (bank), row = 4 (lane >> 4) + reg (query)
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[(wq + 16 * i + 4 * g + e) * KNN_LDS + wn + 16 * j + rr] = acc[i][j][e];
-      __syncthreads();
+      knn_store_tile(sc, acc);
       for (int c = h; c < KNN_BN && n0 + c < p.N; c += 2) knn_offer<KP>(lv[m], li[m], sc[r * KNN_LDS + c], n0 + c);
     }
     if (p.V > p.M) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[(wq + 16 * i + 4 * g + e) * KNN_LDS + wn + 16 * j + rr] = sum[i][j][e];
-      __syncthreads();
+      knn_store_tile(sc, sum);
       for (int c = h; c < KNN_BN && n0 + c < p.N; c += 2) knn_offer<KP>(lv[3], li[3], sc[r * KNN_LDS + c], n0 + c);
     }
   }

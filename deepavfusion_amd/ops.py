@@ -632,7 +632,9 @@ def cast_transpose_grouped(pairs):
 
 # ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------------------------------------
 
-KNN_TILE = 128          # queries per workgroup and bank rows per tile of dav_knn_topk_f32
+KNN_TILE = 128          # queries per workgroup and bank rows per tile of dav_knn_topk_f32 / dav_knn_topk_wide_f32
+KNN_NARROW_K = 8        # longest list of dav_knn_topk_f32 (lists in registers); longer ones go to dav_knn_topk_wide_f32
+KNN_MAX_K = 64          # longest list of dav_knn_topk_wide_f32 (lists in the workspace), and the most neighbours of a vote
 
 
 def knn_splits(Nq, N):
@@ -642,7 +644,8 @@ def knn_splits(Nq, N):
 
 
 def knn_workspace_bytes(Nq, V, k, splits):
-    """splits * V * Nq * k * 8: one (score, index) list per split, view and query (include/dav_kernels.h)."""
+    """splits * V * Nq * k * 8: one (score, index) list per split, view and query — the formula of both top-k entry points,
+    dav_knn_topk_f32 (k <= 8) and dav_knn_topk_wide_f32 (k <= 64) (include/dav_kernels.h)."""
     return splits * V * Nq * k * 8
 
 
@@ -657,7 +660,8 @@ def mean_l2n(x, out=None):
 
 
 def knn_topk(queries, banks, k, sum_view=True, splits=None, out=None, workspace=None):
-    """Top-k bank rows of every query, per modality and (sum_view) for the sum of the modality scores (dav_knn_topk_f32).
+    """Top-k bank rows of every query, per modality and (sum_view) for the sum of the modality scores: dav_knn_topk_f32 for
+    k <= 8, dav_knn_topk_wide_f32 for 8 < k <= 64 (the same scores and the same order: a longer list starts with the shorter one).
     queries / banks: 1-3 fp32 [Nq, D] / [N, D] tensors with unit column stride (a query tensor may be its bank); the sum view
     is (s_0 + s_1) + s_2.  -> (values [V, Nq, k] fp32, indices [V, Nq, k] int64), V = len(queries) + sum_view."""
     M = len(queries)
@@ -681,11 +685,49 @@ def knn_topk(queries, banks, k, sum_view=True, splits=None, out=None, workspace=
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     qp = [_ptr(q) for q in queries] + [None] * (3 - M)
     xp = [_ptr(x) for x in banks] + [None] * (3 - M)
-    _lib.check(_lib.load().dav_knn_topk_f32(qp[0], xp[0], qp[1], xp[1], qp[2], xp[2], M, Nq, N, D, queries[0].stride(0),
-                                            banks[0].stride(0), int(bool(sum_view)), int(k), S, _ptr(out[0]), _ptr(out[1]),
-                                            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
-               'dav_knn_topk_f32')
+    name = 'dav_knn_topk_f32' if k <= KNN_NARROW_K else 'dav_knn_topk_wide_f32'
+    _lib.check(getattr(_lib.load(), name)(qp[0], xp[0], qp[1], xp[1], qp[2], xp[2], M, Nq, N, D, queries[0].stride(0),
+                                          banks[0].stride(0), int(bool(sum_view)), int(k), S, _ptr(out[0]), _ptr(out[1]),
+                                          _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()), name)
     return out[0], out[1].long()
+
+
+def knn_vote(top_val, top_idx, labels, num_classes, k, inv_t, self_offset=-1, out=None):
+    """Weighted vote over top-k lists (dav_knn_vote_f32).  top_val fp32 / top_idx int32 (or int64: converted) [V, Nq, kk] as
+    knn_topk returns them; labels: class ids [N] (any integer dtype: converted to int32) or a multi-hot uint8 [N, C]; inv_t: V
+    floats, w = exp(score * inv_t[v]) (0 -> plain counts); self_offset >= 0 skips the entry whose index is q + self_offset (0: the
+    bank is the query set).  The first k entries that remain vote, so kk >= k, and kk >= k + 1 with an exclusion.
+    -> (scores fp32 [V, Nq, C], pred int64 [V, Nq] = argmax with ties to the lower class, or None for multi-hot labels);
+    ``out`` = (scores, pred int32 or None) to write into."""
+    if top_val.dim() != 3 or top_val.shape != top_idx.shape or top_val.dtype != F32 or not top_val.is_contiguous():
+        raise ValueError('knn_vote needs dense fp32 top_val and top_idx of one shape [V, Nq, kk]')
+    V, Nq, kk = top_val.shape
+    k, C_, self_offset = int(k), int(num_classes), int(self_offset)
+    inv_t = [float(x) for x in inv_t]
+    if len(inv_t) != V:
+        raise ValueError(f'knn_vote needs one inv_t per view: {len(inv_t)} for {V} views')
+    if not 1 <= k <= min(KNN_MAX_K, kk - (self_offset >= 0)):
+        raise ValueError(f'knn_vote: k = {k} neighbours of kk = {kk} entries' + (' less the excluded one' if self_offset >= 0 else '')
+                         + f' (k <= {KNN_MAX_K})')
+    if top_idx.dtype != torch.int32 or not top_idx.is_contiguous():
+        top_idx = top_idx.to(torch.int32).contiguous()
+    multi = labels.dim() == 2
+    if multi:
+        if labels.dtype != torch.uint8 or labels.shape[1] != C_ or not labels.is_contiguous():
+            raise ValueError('knn_vote needs multi-hot labels as dense uint8 [N, num_classes]')
+    elif labels.dim() != 1 or labels.dtype.is_floating_point:
+        raise ValueError('knn_vote needs class ids [N] or multi-hot uint8 [N, num_classes]')
+    elif labels.dtype != torch.int32 or not labels.is_contiguous():
+        labels = labels.to(torch.int32).contiguous()
+    dev = top_val.device
+    if out is None:
+        out = (torch.empty(V, Nq, C_, dtype=F32, device=dev), None if multi else torch.empty(V, Nq, dtype=torch.int32, device=dev))
+    scores, pred = out
+    arr = (C.c_float * V)(*inv_t)
+    _lib.check(_lib.load().dav_knn_vote_f32(_ptr(top_val), _ptr(top_idx), V, Nq, kk, k, None if multi else _ptr(labels),
+                                            _ptr(labels) if multi else None, int(labels.shape[0]), C_, arr, self_offset,
+                                            _ptr(scores), None if multi else _ptr(pred), _stream()), 'dav_knn_vote_f32')
+    return scores, (None if multi else pred.long())
 
 
 # ---- frame transform of the input stage (csrc/data/frames.hip) -----------------------------------------------------------

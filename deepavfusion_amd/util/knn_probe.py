@@ -20,6 +20,13 @@ Documented differences from the reference:
     which are not dependencies of this project.  Python callers may pass any dataset that yields
     ``(image, spec, {'class': label})`` — the reference's contract; multi-hot labels ([num_classes] per clip) select the AP / AUC
     metrics.
+
+Beyond the reference (off unless ``nn_probe.k`` is set; the four metrics above do not change): the weighted k-nearest-neighbour
+classifier of Wu et al. 2018 / DINO.  The bank is a labelled train partition (``bank_partition``, shards; ``bank_samples``,
+synthetic) or, without one, the eval set itself with each query's own row excluded; the k nearest bank rows of a query vote for
+their classes with the weight exp(similarity / temperature) (the sum view on the MEAN similarity of its modalities), by
+dav_knn_topk_wide_f32 + dav_knn_vote_f32.  New keys after the reference's: ``{audio,image,fusion,all}_knn{k}_acc``, or
+``_knn{k}_ap`` / ``_knn{k}_auc`` on the vote scores of multi-hot sets.
 """
 from collections import OrderedDict
 
@@ -36,10 +43,11 @@ _VIEW = {'image': 0, 'audio': 1, 'fusion': 2, 'all': 3}   # kernel views: modali
 
 class SyntheticLabelledAV(torch.utils.data.Dataset):
     """Class c has a fixed seeded prototype frame (ImageNet-normalised scale, N(0, 1)) and log-mel patch (about [-7, 4]); clip i
-    is of class i % num_classes and is its prototype plus seeded Gaussian noise of std ``noise``."""
+    is of class i % num_classes and is its prototype plus seeded Gaussian noise of std ``noise``.  ``offset`` shifts the indices:
+    item i is clip offset + i of the same endless set (a bank disjoint from the eval clips: the same seed, the next indices)."""
 
-    def __init__(self, n, num_classes, image_size, audio_size, seed=0, noise=0.5):
-        self.n, self.num_classes, self.seed, self.noise = n, num_classes, seed, noise
+    def __init__(self, n, num_classes, image_size, audio_size, seed=0, noise=0.5, offset=0):
+        self.n, self.num_classes, self.seed, self.noise, self.offset = n, num_classes, seed, noise, int(offset)
         self.image_size, self.audio_size = tuple(image_size), tuple(audio_size)
         g = torch.Generator().manual_seed(seed * 1_000_003 + 7919)
         self.proto_image = torch.randn(num_classes, 3, *self.image_size, generator=g)
@@ -49,6 +57,7 @@ class SyntheticLabelledAV(torch.utils.data.Dataset):
         return self.n
 
     def __getitem__(self, i):
+        i = i + self.offset
         c = i % self.num_classes
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + 104_729 + i)
         image = self.proto_image[c] + self.noise * torch.randn(3, *self.image_size, generator=g)
@@ -109,6 +118,35 @@ def probe_metrics(preds, labels, multi_label):
     return dict(out)
 
 
+def vote_metrics(scores, preds, labels, multi_label, k):
+    """The weighted-vote keys, in the order of ``scores``: scores = {modality: vote scores [n, C]}, preds = {modality: voted
+    class [n]} (single-label; unused for multi-hot), labels [n] or multi-hot [n, C] of the QUERIES (numpy) ->
+    {'<mod>_knn<k>_acc'} or {'<mod>_knn<k>_ap', '<mod>_knn<k>_auc'} (AP / AUC over the classes that occur among the queries)."""
+    out = OrderedDict()
+    if multi_label:
+        seen = labels.sum(0) > 0
+        for mod, sc in scores.items():
+            out[f'{mod}_knn{k}_ap'] = float(average_precision(labels[:, seen], sc[:, seen]).mean())
+            out[f'{mod}_knn{k}_auc'] = float(roc_auc(labels[:, seen], sc[:, seen]).mean())
+    else:
+        for mod in scores:
+            out[f'{mod}_knn{k}_acc'] = float(np.mean(preds[mod] == labels) * 100)
+    return dict(out)
+
+
+def knn_vote_predictions(feats, bank_feats, bank_labels, num_classes, k, temperature, exclude_self):
+    """feats / bank_feats = (image, audio, fusion) features [n, D] / [N, D]; bank_labels class ids [N] or multi-hot [N, C].
+    -> {modality: (vote scores [n, C], voted class [n] or None)} (device tensors).  ``exclude_self``: the bank IS the query set, row
+    q of it is skipped for query q (one more entry is fetched for it)."""
+    kk = k + int(bool(exclude_self))
+    val, idx = ops.knn_topk(feats, bank_feats, k=kk, sum_view=True)
+    M = len(feats)
+    inv_t = [1.0 / temperature] * M + [1.0 / (temperature * M)]              # the sum view votes on the mean similarity
+    lab = bank_labels.to(torch.uint8) if bank_labels.dim() == 2 else bank_labels
+    scores, pred = ops.knn_vote(val, idx, lab, num_classes, k, inv_t, self_offset=0 if exclude_self else -1)
+    return OrderedDict((mod, (scores[_VIEW[mod]], None if pred is None else pred[_VIEW[mod]])) for mod in MODALITIES)
+
+
 def knn_predictions(v_feats, a_feats, mm_feats, labels, k=2):
     """util/knn_probe.py:113-131 as ONE kernel call: -> {modality: (labels of the 2nd neighbour, its score)} (device tensors)."""
     val, idx = ops.knn_topk((v_feats, a_feats, mm_feats), (v_feats, a_feats, mm_feats), k=k, sum_view=True)
@@ -116,7 +154,7 @@ def knn_predictions(v_feats, a_feats, mm_feats, labels, k=2):
 
 
 class EvalAVNNProbe:
-    def __init__(self, probe_args, log_args, env_args, dataset=None):
+    def __init__(self, probe_args, log_args, env_args, dataset=None, bank_dataset=None):
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.distributed = dist_utils.get_world_size() > 1
         self.eval_freq = int(log_args.eval_freq)
@@ -124,6 +162,16 @@ class EvalAVNNProbe:
         self.dataset = probe_args.get('dataset') if dataset is None else 'custom'
         self.seed = int(env_args.get('seed') or 0)
         self.frame_frontend = self.audio_frontend = None       # shards: raw frames / waveforms in, transforms on the device
+        self.k = None if probe_args.get('k') is None else int(probe_args.get('k'))            # None: the reference's protocol only
+        self.temperature = float(probe_args.get('temperature') or 0.07)
+        if self.k is not None and not 1 <= self.k < ops.KNN_MAX_K:
+            raise ValueError(f'nn_probe.k={self.k}: the weighted vote takes 1 .. {ops.KNN_MAX_K - 1} neighbours')
+        if self.k is not None and not self.temperature > 0:
+            raise ValueError(f'nn_probe.temperature={self.temperature} must be positive')
+        self.bank_db = bank_dataset
+        bank_samples, bank_partition = probe_args.get('bank_samples'), probe_args.get('bank_partition')
+        if self.k is None and (bank_dataset is not None or bank_samples or bank_partition):
+            raise ValueError('a bank (nn_probe.bank_samples / bank_partition) is used by the weighted vote only: set nn_probe.k')
         if dataset is not None:
             self.db, self.multi_label = dataset, None          # decided by the label shape
         elif self.dataset == 'synthetic':
@@ -132,6 +180,8 @@ class EvalAVNNProbe:
             self.db = SyntheticLabelledAV(int(probe_args.num_samples), int(probe_args.num_classes), image_size, audio_size,
                                           seed=self.seed)
             self.multi_label = False
+            if bank_partition:
+                raise ValueError('nn_probe.bank_partition names a shard partition; the synthetic set takes nn_probe.bank_samples')
         elif self.dataset == 'shards':
             from . import audio_transforms as aT
             from .clip_shards import ClipShards
@@ -143,6 +193,13 @@ class EvalAVNNProbe:
             if not self.db.has_labels:
                 raise ValueError(f'{self.db.dir} has no labels.npy: the nearest-neighbour probe needs a labelled shard set')
             self.multi_label = self.db.multi_label
+            if bank_samples:
+                raise ValueError('nn_probe.bank_samples belongs to the synthetic set; shards take nn_probe.bank_partition')
+            if bank_partition:
+                self.bank_db = ClipShards(probe_args.data_path, bank_partition, audio_dur=float(probe_args.audio_dur),
+                                          audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed)
+                if not self.bank_db.has_labels or self.bank_db.multi_label != self.multi_label:
+                    raise ValueError(f'{self.bank_db.dir}: the bank needs labels of the same kind as {self.db.dir}')
             self.frame_frontend = EvalFrameTransform(int(probe_args.image_size))
             self.audio_frontend = aT.Compose([aT.Pad(float(probe_args.audio_dur), int(probe_args.audio_rate)),
                                               aT.LogMelSpectrogram(int(probe_args.audio_rate), int(probe_args.audio_mels))])
@@ -151,6 +208,12 @@ class EvalAVNNProbe:
                                       '(the reference datasets need PyAV/torchaudio; decode them with tools/make_shards.py)')
         else:
             raise NotImplementedError(f'nn_probe.dataset={self.dataset}')
+        if bank_samples:                                       # the next bank_samples clips of the same synthetic set
+            if not isinstance(self.db, SyntheticLabelledAV) or bank_dataset is not None:
+                raise ValueError('nn_probe.bank_samples needs the synthetic set (and no bank_dataset)')
+            d = self.db
+            self.bank_db = SyntheticLabelledAV(int(bank_samples), d.num_classes, d.image_size, d.audio_size, seed=d.seed,
+                                               noise=d.noise, offset=d.offset + len(d))
         if self.distributed:
             self.generator = None
             self.sampler = torch.utils.data.DistributedSampler(self.db, num_replicas=dist_utils.get_world_size(),
@@ -160,6 +223,16 @@ class EvalAVNNProbe:
             self.sampler = torch.utils.data.RandomSampler(self.db, generator=self.generator)
         self.loader = torch.utils.data.DataLoader(self.db, sampler=self.sampler, batch_size=max(int(probe_args.batch_size) // 4, 1),
                                                   num_workers=int(env_args.get('workers') or 0), pin_memory=False, drop_last=True)
+        self.bank_loader = None
+        if self.bank_db is not None:
+            # every bank clip once, in order (no drop_last); ranks take contiguous runs of equal length for the gather, which leaves
+            # out at most world_size - 1 clips at the end of the set
+            world, rank = dist_utils.get_world_size(), dist_utils.get_rank()
+            per = len(self.bank_db) // world
+            self.bank_loader = torch.utils.data.DataLoader(
+                torch.utils.data.Subset(self.bank_db, range(rank * per, (rank + 1) * per)), shuffle=False,
+                batch_size=max(int(probe_args.batch_size) // 4, 1), num_workers=int(env_args.get('workers') or 0),
+                pin_memory=False, drop_last=False)
 
     @torch.no_grad()
     def extract(self, model):
@@ -169,11 +242,20 @@ class EvalAVNNProbe:
             self.sampler.set_epoch(0)
         else:
             self.generator.manual_seed(self.seed)
+        return self._extract(model, self.loader)
+
+    @torch.no_grad()
+    def extract_bank(self, model):
+        """The bank's features and labels, as ``extract`` (eval transforms, LayerNorm folding off, gathered over the group)."""
+        model.train(False)
+        return self._extract(model, self.bank_loader)
+
+    def _extract(self, model, loader):
         feats, labels = ([], [], []), []
         prev = E.LN_FUSE_MODE
         E.set_ln_fuse('off')
         try:
-            for image, spec, anno in self.loader:
+            for image, spec, anno in loader:
                 spec = spec.to(self.device, non_blocking=True).float()
                 image = image.to(self.device, non_blocking=True)
                 image = self.frame_frontend(image) if self.frame_frontend is not None else image.float()
@@ -193,5 +275,23 @@ class EvalAVNNProbe:
         v_feats, a_feats, mm_feats, labels = self.extract(model)
         preds = knn_predictions(v_feats, a_feats, mm_feats, labels)
         multi_label = self.multi_label if self.multi_label is not None else labels.dim() == 2
-        return probe_metrics(OrderedDict((m, (p.cpu().numpy(), s.cpu().numpy())) for m, (p, s) in preds.items()),
-                             labels.cpu().numpy(), multi_label)
+        out = probe_metrics(OrderedDict((m, (p.cpu().numpy(), s.cpu().numpy())) for m, (p, s) in preds.items()),
+                            labels.cpu().numpy(), multi_label)
+        if self.k is not None:
+            out.update(self._vote(model, (v_feats, a_feats, mm_feats), labels, multi_label))
+        return out
+
+    def _vote(self, model, feats, labels, multi_label):
+        if self.bank_loader is not None:
+            *bank, bank_labels = self.extract_bank(model)
+        else:
+            bank, bank_labels = feats, labels                  # the eval set against itself, each query's own row excluded
+        if multi_label:
+            C = labels.shape[1]
+        else:
+            C = int(torch.maximum(labels.max(), bank_labels.max())) + 1
+        votes = knn_vote_predictions(feats, tuple(bank), bank_labels, C, self.k, self.temperature,
+                                     exclude_self=self.bank_loader is None)
+        return vote_metrics(OrderedDict((m, s.cpu().numpy()) for m, (s, _) in votes.items()),
+                            None if multi_label else OrderedDict((m, p.cpu().numpy()) for m, (_, p) in votes.items()),
+                            labels.cpu().numpy(), multi_label, self.k)

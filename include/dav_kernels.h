@@ -37,7 +37,7 @@ typedef struct ihipStream_t* hipStream_t;
 extern "C" {
 #endif
 
-#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) (9 also: dav_mean_l2n_f32, dav_knn_topk_f32, dav_frame_transform_u8) */
+#define DAV_ABI_VERSION 9   /* 9: dropout (dav_attn_drop_fwd / _bwd (+ _f32), dav_dropout_rows); 8: LayerNorm folded into the GEMMs either side of it (dav_gemm_nt_ln_bf16, dav_ln_fold_grouped, dav_rowstats_cast, dav_layernorm_bwd_twin); 2: DavTnProblem.flags, dav_adamw_flat keep_grad + gscale_dev, dav_step_guard; 3: dav_attn_bwd_ctx, dav_add_cast; 4: fused fusion tails, grouped cast-transpose; 5: dav_gemm_tn_grouped_adamw_bf16; 6: dav_gemm_tn_gang_bf16; 7: the fused fusion tails and dav_gemm_tn_grouped_adamw_bf16 are gone (measured slower, DESIGN_HISTORY section 11) (9 also: dav_mean_l2n_f32, dav_knn_topk_f32, dav_frame_transform_u8, dav_knn_topk_wide_f32, dav_knn_vote_f32) */
 int dav_abi_version(void);
 int dav_build_flags(void);   /* bit 0: experimental build (make EXPERIMENTAL=1): the rejected GEMM tile configurations exist */
 /* text of the last HIP error latched by a kernel launch of the calling thread (diagnostics) */
@@ -412,6 +412,36 @@ int dav_mean_l2n_f32(const float* x, int B, int L, int D, long ld_row, long ld_b
 int dav_knn_topk_f32(const float* q0, const float* x0, const float* q1, const float* x1, const float* q2, const float* x2, int M,
                      int Nq, int N, int D, long ldq, long ldx, int sum_view, int k, int splits, float* top_val, int* top_idx,
                      void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* The weighted k-NN probe (Wu et al. 2018, DINO; csrc/probe/knn_wide.hip) — not in the reference, whose probe stops at the nearest
+ * other clip.  dav_knn_topk_wide_f32 is dav_knn_topk_f32 with 1 <= k <= min(64, N): the same operands, views, splits and output
+ * layout, the same score chains in the same order (the two share their tile code), the same strict order (score descending, ties to
+ * the LOWER bank index).  So for k <= 8 it equals dav_knn_topk_f32 bit for bit, the first 8 entries of a longer list equal that
+ * kernel's k = 8 result, and the result is the same for every split count, query chunking and arrival order of the bank rows.
+ * The lists live in the workspace while the bank streams by, one per (split, view, query); a second launch merges the splits:
+ * workspace_bytes >= splits * V * Nq * k * 8 (8-byte aligned) — the formula of dav_knn_topk_f32 (deepavfusion_amd.ops
+ * .knn_workspace_bytes).  No [Nq, N] score matrix exists in memory.
+ * -1: an empty input, M outside 1..3, k < 1, k > 64, k > N, D % 4, a stride below D, splits outside 1..65535, a NULL operand or
+ * output; -3: a NULL or short workspace; -5: q_m / x_m not 16-byte aligned, ldq / ldx not multiples of 4, outputs not 4-byte,
+ * workspace not 8-byte aligned. */
+int dav_knn_topk_wide_f32(const float* q0, const float* x0, const float* q1, const float* x1, const float* q2, const float* x2,
+                          int M, int Nq, int N, int D, long ldq, long ldx, int sum_view, int k, int splits, float* top_val,
+                          int* top_idx, void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* The vote over such lists.  top_val / top_idx [V, Nq, kk] as either top-k kernel writes them (V in 1..4).  For every (view v,
+ * query q) the entries are walked in order; an entry whose index is q + self_offset is skipped (self_offset = -1: none is — the
+ * bank is another set; 0: the bank is the query set itself); the first k remaining entries j vote with the weight
+ * w_j = expf(top_val_j * inv_t[v]) for the class labels[idx_j] (labels int32 [N]) or for every set class of the row
+ * multihot[idx_j, :] (uint8 [N, C]); exactly one of labels / multihot is given.  inv_t is a HOST array of V floats, read before the
+ * call returns (1 / T for a modality; 1 / (T M) for the sum view votes on the mean similarity; 0 gives plain counts).
+ * scores fp32 [V, Nq, C] (every element written); pred int32 [V, Nq] = the class of the largest score, ties to the LOWER class
+ * (required with labels, ignored with multihot).  The k weights of a class are added in entry order, so the result is repeatable
+ * bit for bit.  An index outside [0, N) and a label outside [0, C) vote for nothing.  1 <= k <= min(64, kk), and k <= kk - 1 when
+ * self_offset >= 0: k entries must remain whatever the exclusion removes.
+ * -1: an empty input, V outside 1..4, k outside that range, C < 1, self_offset < -1, a NULL top_val / top_idx / inv_t / scores,
+ * neither or both of labels / multihot, labels without pred; -5: top_val, top_idx, labels, scores or pred not 4-byte aligned.
+ * One launch, no workspace. */
+int dav_knn_vote_f32(const float* top_val, const int* top_idx, int V, int Nq, int kk, int k, const int* labels,
+                     const uint8_t* multihot, int N, int C, const float* inv_t, int self_offset, float* scores, int* pred,
+                     hipStream_t stream);
 
 /* ---- fp32-operand twins (csrc/f32_path.hip) ------------------------------------------------ */
 /* The same contracts as the bf16 entry points above with every operand, second output and intermediate in fp32 (plain
