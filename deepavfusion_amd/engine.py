@@ -17,7 +17,7 @@ final through ``set_grad_ready_hook``.
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -776,41 +776,81 @@ def ln_bwd_tw(norm, eps, t0, r0, t1, r1, B, dy_bf16=None, dy_f32=None, *, h_out=
         _DEFERRED_LN_READY.append((norm.weight, norm.bias))
 
 
-def attention_fwd(q, k, v, B, H, Nq, Nk, dqk, dv, scale, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, dev, keep=None):
-    """q/k/v are (tensor, element_offset) pairs into bf16 buffers. Returns O [B*Nq, H*dv] bf16 and LSE.
-    ``keep`` = (bytes 0 / 1 [B, H, Nq, ld], ld, 1 / (1 - p)): attention dropout (see draw_attn_keep)."""
+class AttnView(NamedTuple):
+    """An attention operand: columns [c0, c0 + H * d) of rows [r0, r0 + N) of every batch element of a contiguous row-major buffer
+    [B * rows, ld].  ``off`` = element offset of the first element, ``bs`` / ``rs`` = batch / row stride in elements."""
+    t: torch.Tensor
+    off: int
+    bs: int
+    rs: int
+
+
+def cols(buf, rows, c0=0, r0=0):
+    """The operand that starts at column ``c0`` of row ``r0`` of each batch element of ``buf`` [B * rows, ld]."""
+    ld = buf.shape[1]
+    return AttnView(buf, r0 * ld + c0, rows * ld, ld)
+
+
+def qkv_cols(qkv, rows, D, r0=0):
+    """(q, k, v) of a packed projection [B * rows, 3D]: column blocks 0 / D / 2D; the queries start ``r0`` rows in (context rows
+    in front of them are keys and values only)."""
+    return cols(qkv, rows, 0, r0), cols(qkv, rows, D), cols(qkv, rows, 2 * D)
+
+
+def _attn_ptr(name, v, B, N, width, r0_is=0):
+    """Address of the first element of operand ``v`` after checking that ``N`` rows of ``width`` = H * d columns per batch element
+    stay inside its buffer: a wrong stride or offset must fail here, not read or write outside the buffer on the GPU."""
+    t, off, bs, rs = v
+    ok = t.dim() == 2 and t.is_contiguous() and off >= 0 and rs == t.shape[1] and rs > 0 and bs % rs == 0 and t.shape[0] == B * (bs // rs)
+    if ok:
+        r0, c0 = divmod(off, rs)
+        ok = c0 + width <= rs and r0 + N <= bs // rs and (not r0_is or r0 == r0_is)
+    if not ok:
+        raise ValueError(f'attention operand {name}: (off, bs, rs) = {tuple(v[1:])} into {tuple(t.shape)} (contiguous: {t.is_contiguous()}) '
+                         f'does not hold {B} x {N} rows of {width} columns' + (f' from row {r0_is}' if r0_is else ''))
+    return t.data_ptr() + t.element_size() * off
+
+
+def attention_fwd(q, k, v, B, H, Nq, Nk, dqk, dv, scale, keep=None, bias=None):
+    """q / k / v: AttnView.  Returns O [B*Nq, H*dv] (operand dtype) and LSE.
+    ``keep`` = (bytes 0 / 1 [B, H, Nq, ld], ld, 1 / (1 - p)): attention dropout (see draw_attn_keep);
+    ``bias`` = (additive logit bias [nb, H, Nq, ld] fp32, nb, ld) (see swin_block_fwd)."""
+    ptrs = (_attn_ptr('q', q, B, Nq, H * dqk), _attn_ptr('k', k, B, Nk, H * dqk), _attn_ptr('v', v, B, Nk, H * dv))
+    dev = q.t.device
     O = _e((B * Nq, H * dv), BF16, dev)
     LSE = _e((B, H, Nq), F32, dev)
-    ops.hold(q[0], k[0], v[0])
-    es = q[0].element_size()
+    ops.hold(q.t, k.t, v.t)
+    args = (*ptrs, O, LSE, B, H, Nq, Nk, dqk, dv, q.bs, q.rs, k.bs, k.rs, v.bs, v.rs, Nq * H * dv, H * dv, scale)
     if keep is not None:
-        ops.attn_drop_fwd(q[0].data_ptr() + es * q[1], k[0].data_ptr() + es * k[1], v[0].data_ptr() + es * v[1], O, LSE, B, H, Nq, Nk,
-                          dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, Nq * H * dv, H * dv, scale, keep[0], keep[1], keep[2])
-        return O, LSE
-    ops.attn_fwd(q[0].data_ptr() + es * q[1], k[0].data_ptr() + es * k[1], v[0].data_ptr() + es * v[1], O, LSE, B, H, Nq, Nk,
-                 dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, Nq * H * dv, H * dv, scale)
+        ops.attn_drop_fwd(*args, *keep)
+    elif bias is not None:
+        ops.attn_bias_fwd(*args, *bias)
+    else:
+        ops.attn_fwd(*args)
     return O, LSE
 
 
 _ATTN_CTX = True      # (False: a torch fill pass zeroes the context rows' dq slots, rounds 1-2)
 
 
-def attention_bwd(q, k, v, O, dO, LSE, dq, dk, dvv, B, H, Nq, Nk, dqk, dv, scale, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs,
-                  dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, part=3, Delta=None, dq_ctx_rows=0, keep=None):
-    """``part`` 1 / 2: only the dQ (+ Delta) / only the dK-dV kernel, with the same ``Delta`` buffer passed to both calls
-    (lets a caller put the two kernels of several attentions into two regions of a launch batch)."""
+def attention_bwd(q, k, v, O, dO, LSE, dq, dk, dv_, B, H, Nq, Nk, dqk, dv, scale, part=3, Delta=None, dq_ctx_rows=0, keep=None,
+                  bias=None, dS=None):
+    """q / k / v and their gradient buffers dq / dk / dv_: AttnView.  ``part`` 1 / 2: only the dQ (+ Delta) / only the dK-dV kernel,
+    with the same ``Delta`` buffer passed to both calls (lets a caller put the two kernels of several attentions into two regions
+    of a launch batch).  ``bias`` as in attention_fwd, ``dS`` [B, H, Nq, ld] fp32 receives the gradient of the biased logits."""
+    ptrs = (_attn_ptr('q', q, B, Nq, H * dqk), _attn_ptr('k', k, B, Nk, H * dqk), _attn_ptr('v', v, B, Nk, H * dv),
+            _attn_ptr('dq', dq, B, Nq, H * dqk, dq_ctx_rows), _attn_ptr('dk', dk, B, Nk, H * dqk), _attn_ptr('dv', dv_, B, Nk, H * dv))
     if Delta is None:
         Delta = torch.empty_like(LSE)
-    ops.hold(q[0], k[0], v[0], dq[0], dk[0], dvv[0])
-    p = lambda t: t[0].data_ptr() + t[0].element_size() * t[1]
+    ops.hold(q.t, k.t, v.t, dq.t, dk.t, dv_.t)
+    args = (*ptrs[:3], O, dO, LSE, Delta, *ptrs[3:], B, H, Nq, Nk, dqk, dv, q.bs, q.rs, k.bs, k.rs, v.bs, v.rs,
+            Nq * H * dv, H * dv, Nq * H * dv, H * dv, dq.bs, dq.rs, dk.bs, dk.rs, dv_.bs, dv_.rs, scale)
     if keep is not None:
-        ops.attn_drop_bwd(p(q), p(k), p(v), O, dO, LSE, Delta, p(dq), p(dk), p(dvv), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
-                          v_bs, v_rs, Nq * H * dv, H * dv, Nq * H * dv, H * dv, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, scale,
-                          keep[0], keep[1], keep[2], part=part, dq_ctx_rows=dq_ctx_rows)
-        return
-    ops.attn_bwd(p(q), p(k), p(v), O, dO, LSE, Delta, p(dq), p(dk), p(dvv), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
-                 v_bs, v_rs, Nq * H * dv, H * dv, Nq * H * dv, H * dv, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, scale, part=part,
-                 dq_ctx_rows=dq_ctx_rows)
+        ops.attn_drop_bwd(*args, *keep, part=part, dq_ctx_rows=dq_ctx_rows)
+    elif bias is not None:
+        ops.attn_bias_bwd(*args, *bias, dS, part=part)
+    else:
+        ops.attn_bwd(*args, part=part, dq_ctx_rows=dq_ctx_rows)
 
 
 def to_bf16(x):
@@ -893,8 +933,7 @@ def block_fwd(blk, x_mod, x_fus, heads, eps, dp=None, idle_before_mlp=0, dr=None
     dr = dr or {}
     h1, _, st1 = ln_fwd(blk.norm1, x_fus, x_mod, B, eps)
     qkv = lin_fwd(blk.attn.qkv, h1, M, out_bf16=True)                                       # [B*R, 3D]
-    o, lse = attention_fwd((qkv, nF * 3 * D), (qkv, D), (qkv, 2 * D), B, heads, n, R, hd, hd, hd ** -0.5,
-                           R * 3 * D, 3 * D, R * 3 * D, 3 * D, R * 3 * D, 3 * D, dev, keep=dr.get('attn'))
+    o, lse = attention_fwd(*qkv_cols(qkv, R, D, nF), B, heads, n, R, hd, hd, hd ** -0.5, keep=dr.get('attn'))
     x1 = _res_add(blk.attn.proj, o, Mq, x_mod, B, n, D, None if dp is None else dp[0], drop=dr.get('proj')).view(B, n, D)
     lane_skip(idle_before_mlp)          # batched beside a fusion block: line norm2 / fc1 / fc2 up with its norm2 / fc1 / fc2
     h2, _, st2 = ln_fwd(blk.norm2, None, x1, B, eps)
@@ -923,8 +962,7 @@ def _block_fwd_ln(blk, x_mod, x_fus, heads, eps, idle_before_mlp=0):
         qkv = lin_fwd_ln(blk.attn.qkv, blk.norm1, eps, tf, M, t1=tm, r0=nF, r1=n)            # [B*R, 3D]
     else:
         qkv = lin_fwd_ln(blk.attn.qkv, blk.norm1, eps, tm, M)
-    o, lse = attention_fwd((qkv, nF * 3 * D), (qkv, D), (qkv, 2 * D), B, heads, n, R, hd, hd, hd ** -0.5,
-                           R * 3 * D, 3 * D, R * 3 * D, 3 * D, R * 3 * D, 3 * D, dev)
+    o, lse = attention_fwd(*qkv_cols(qkv, R, D, nF), B, heads, n, R, hd, hd, hd ** -0.5)
     x1, tw1 = lin_fwd_tw(blk.attn.proj, o, Mq, x_mod)
     lane_skip(idle_before_mlp)
     Hd = blk.mlp.fc1.weight.shape[0]
@@ -984,11 +1022,8 @@ def block_bwd_head(blk, t, g2, g2b, idle_before_attn=0):
     ctx_in_kernel = PRECISION != 'fp32' and _ATTN_CTX
     if nF > 0 and not ctx_in_kernel:
         dqkv.view(B, R, 3 * D)[:, :nF, :D].zero_()
-    qkv = t['qkv']
-    attention_bwd((qkv, nF * 3 * D), (qkv, D), (qkv, 2 * D), t['o'], do, t['lse'],
-                  (dqkv, nF * 3 * D), (dqkv, D), (dqkv, 2 * D), B, heads, n, R, hd, hd, hd ** -0.5,
-                  R * 3 * D, 3 * D, R * 3 * D, 3 * D, R * 3 * D, 3 * D,
-                  R * 3 * D, 3 * D, R * 3 * D, 3 * D, R * 3 * D, 3 * D, dq_ctx_rows=nF if ctx_in_kernel else 0, keep=dr.get('attn'))
+    attention_bwd(*qkv_cols(t['qkv'], R, D, nF), t['o'], do, t['lse'], *qkv_cols(dqkv, R, D, nF), B, heads, n, R, hd, hd, hd ** -0.5,
+                  dq_ctx_rows=nF if ctx_in_kernel else 0, keep=dr.get('attn'))
     if fused:
         dh1 = lin_bwd(blk.attn.qkv, dqkv, None, M, wgrad=False)
         return dict(dh1=dh1, g1=g1, dqkv=dqkv)
@@ -1033,6 +1068,65 @@ def block_bwd_tail(blk, t, st, *, dx_fus=None, dx_fus_acc=0, dx_mod=None, dx_mod
     return dx_mod, dx_mod_b, dx_fus
 
 
+# ---- what the three fusion blocks share: the norm2 + MLP tail (models/fusion_blocks.py:286-288), the three input LayerNorms' backward
+def _mlp_tail_fwd(fb, xmm1, B, nF, D, dev, dp=None, dr=None, z=None):
+    """xmm1 + [DropPath] mlp(norm2(xmm1)) -> (out fp32 [B,nF,D], tape entries).  ``z``: GELU-input buffer a caller allocated earlier."""
+    dr = dr or {}
+    h2, _, st2 = ln_fwd(fb.norm2, None, xmm1, B)
+    Hd = fb.mlp.fc1.weight.shape[0]
+    if z is None:
+        z = _e((B * nF, Hd), BF16, dev)
+    u = lin_fwd(fb.mlp.fc1, h2, B * nF, act=1, out_bf16=True, C2=z, c2_mode=4)
+    if 'fc1' in dr:
+        _drop(u, dr['fc1'], B, nF, Hd)
+    out = _res_add(fb.mlp.fc2, u, B * nF, xmm1, B, nF, D, None if dp is None else dp[1], drop=dr.get('fc2')).view(B, nF, D)
+    return out, dict(h2=h2, st2=st2, z=z, u=u, xmm1=xmm1, dp=dp, dr=dr or None)
+
+
+def _mlp_tail_bwd(fb, tt, g, gb, B, nF, D, dev, g1_first=False):
+    """-> (g1 fp32 [B,nF,D], g1b bf16): gradient at xmm1 (the attention residual output) as the norm2 backward leaves it; the caller
+    rescales g1b into the gradient of its attention BRANCH (DropPath, dropout), g1 stays the residual-path gradient.
+    ``g1_first``: allocate the two in front of fc1's input gradient (the region form's order) instead of behind it."""
+    dp = tt.get('dp')
+    dr = tt.get('dr') or {}
+    if dp is not None or 'fc2' in dr:
+        gb = _branch_grad(g, None if dp is None else dp[1], dr.get('fc2'), B, nF, D)
+    elif gb is None:
+        gb = to_bf16(g)
+    dz = lin_bwd(fb.mlp.fc2, gb, tt['u'], B * nF, gelu_aux=tt['z'])
+    if 'fc1' in dr:
+        _drop(dz, dr['fc1'], B, nF, dz.shape[1])
+    bufs = lambda: (_e((B, nF, D), F32, dev), _e((B * nF, D), BF16, dev))
+    g1, g1b = bufs() if g1_first else (None, None)
+    dh2 = lin_bwd(fb.mlp.fc1, dz, tt['h2'], B * nF)
+    if g1 is None:
+        g1, g1b = bufs()
+    ln_bwd(fb.norm2, None, tt['xmm1'], B, tt['st2'], dy_bf16=dh2, dx1=g1, res1=g, dx1_bf16=g1b)
+    return g1, g1b
+
+
+def _input_norms_bwd(fb, t, side0, side1, dxmm_b, g1, dx_i, dx_a, dx_f_first=False):
+    """Backward of the two side LayerNorms, in the caller's launch order — side = (norm, x, statistics, dy bf16), the first one's input
+    gradient goes to ``dx_i``, the second one's to ``dx_a`` (accumulated into when passed, else allocated and stored) — and then of
+    norm1_mm (dy = dxmm_b + the residual-path gradient g1) -> (dx_f, dx_i, dx_a).  ``dx_f_first``: allocate dx_f before the first
+    launch (the region form's order) instead of after the side launches."""
+    x_f = t['x_f']
+    B, _, D = x_f.shape
+    new = lambda x: _e((B, x.shape[1], D), F32, x.device)
+    acc_i, acc_a = (1 if dx_i is not None else 0), (1 if dx_a is not None else 0)
+    if dx_i is None:
+        dx_i = new(side0[1])
+    if dx_a is None:
+        dx_a = new(side1[1])
+    dx_f = new(x_f) if dx_f_first else None
+    ln_bwd(side0[0], None, side0[1], B, side0[2], dy_bf16=side0[3], dx1=dx_i, acc1=acc_i)
+    ln_bwd(side1[0], None, side1[1], B, side1[2], dy_bf16=side1[3], dx1=dx_a, acc1=acc_a)
+    if dx_f is None:
+        dx_f = new(x_f)
+    ln_bwd(fb.norm1_mm, None, x_f, B, t['st_mm'], dy_bf16=dxmm_b, dy_f32=g1, dx1=dx_f)
+    return dx_f, dx_i, dx_a
+
+
 # ------------------------------------------------------------------------------------------------
 # FusionBlock_FactorizedAVInteractions (models/fusion_blocks.py:216-289)
 # ------------------------------------------------------------------------------------------------
@@ -1071,10 +1165,8 @@ def _factorized_fwd(fb, x_f, x_i, x_a, heads, tkns, dp=None, dr=None):
             kv_a = lin_fwd(at.attn_a.kv, xa_b, B * nA, out_bf16=True)
         q2 = lin_fwd(at.q, xmm_b, B * nmm, a_rowmap=rm2, out_bf16=True)                      # [B*nmm, Da]
     with region():
-        o_v, lse_v = attention_fwd((q_v, 0), (kv_v, 0), (kv_v, D), B, heads, nv, nI, hd, hd, hd ** -0.5,
-                                   nv * D, D, nI * 2 * D, 2 * D, nI * 2 * D, 2 * D, dev)
-        o_a, lse_a = attention_fwd((q_a, 0), (kv_a, 0), (kv_a, D), B, heads, na, nA, hd, hd, hd ** -0.5,
-                                   na * D, D, nA * 2 * D, 2 * D, nA * 2 * D, 2 * D, dev)
+        o_v, lse_v = attention_fwd(cols(q_v, nv), cols(kv_v, nI), cols(kv_v, nI, D), B, heads, nv, nI, hd, hd, hd ** -0.5)
+        o_a, lse_a = attention_fwd(cols(q_a, na), cols(kv_a, nA), cols(kv_a, nA, D), B, heads, na, nA, hd, hd, hd ** -0.5)
     cv, ca = dict(q=q_v, kv=kv_v, o=o_v, lse=lse_v), dict(q=q_a, kv=kv_a, o=o_a, lse=lse_a)
     xmm1 = _e((B, nF, D), F32, dev)
     # proj of the two aggregations: fp32 result lands in its rows of xmm1 (+ normed-xmm residual),
@@ -1101,8 +1193,7 @@ def _factorized_fwd(fb, x_f, x_i, x_a, heads, tkns, dp=None, dr=None):
         ops.pair_expand(kv_p, ka_p, B, nv, na, Da, Kp)
         ops.pair_expand(vv_p, va_p, B, nv, na, D, Vp)
     scale = hd ** -0.5                                                                       # NOT (Da/heads)^-0.5 (:220-222)
-    o2, lse2 = attention_fwd((q2, 0), (Kp, 0), (Vp, 0), B, heads, nmm, P, Da // heads, hd, scale,
-                             nmm * Da, Da, P * Da, Da, P * D, D, dev)
+    o2, lse2 = attention_fwd(cols(q2, nmm), cols(Kp, P), cols(Vp, P), B, heads, nmm, P, Da // heads, hd, scale)
     Hd = fb.mlp.fc1.weight.shape[0]
     z = _e((B * nF, Hd), BF16, dev)
     if fused:
@@ -1110,14 +1201,12 @@ def _factorized_fwd(fb, x_f, x_i, x_a, heads, tkns, dp=None, dr=None):
         u = lin_fwd_ln(fb.mlp.fc1, fb.norm2, fb.norm2.eps, tw1, B * nF, act=1, C2=z, c2_mode=4)
         out, two = lin_fwd_tw(fb.mlp.fc2, u, B * nF, xmm1_2d)
         out = tw_set(out.view(B, nF, D), *two)
-        h2 = st2 = None
+        tt = dict(h2=None, st2=None, z=z, u=u, xmm1=xmm1, dp=None)
     else:
         lin_fwd(at.proj, o2, B * nmm, res=xmm32, res_rowmap=rm2, out=xmm1, c_rowmap=rm2)
-        h2, _, st2 = ln_fwd(fb.norm2, None, xmm1, B)
-        u = lin_fwd(fb.mlp.fc1, h2, B * nF, act=1, out_bf16=True, C2=z, c2_mode=4)
-        out = lin_fwd(fb.mlp.fc2, u, B * nF, res=xmm1).view(B, nF, D)
-    tape = dict(dp=None, x_f=x_f, x_i=x_i, x_a=x_a, xmm_b=xmm_b, st_mm=st_mm, xv_b=xv_b, st_v=st_v, xa_b=xa_b, st_a=st_a, cv=cv, ca=ca,
-                xvo_b=xvo_b, xao_b=xao_b, Kp=Kp, Vp=Vp, q2=q2, o2=o2, lse2=lse2, xmm1=xmm1, h2=h2, st2=st2, z=z, u=u,
+        out, tt = _mlp_tail_fwd(fb, xmm1, B, nF, D, dev, z=z)
+    tape = dict(tt, x_f=x_f, x_i=x_i, x_a=x_a, xmm_b=xmm_b, st_mm=st_mm, xv_b=xv_b, st_v=st_v, xa_b=xa_b, st_a=st_a, cv=cv, ca=ca,
+                xvo_b=xvo_b, xao_b=xao_b, Kp=Kp, Vp=Vp, q2=q2, o2=o2, lse2=lse2,
                 heads=heads, tkns=tkns, ln_fused=fused, ti=ti if fused else None, ta=ta if fused else None, tw1=tw1)
     return out, tape
 
@@ -1137,27 +1226,25 @@ def _factorized_bwd(fb, t, g, gb, *, dx_i=None, dx_a=None):
     P = nv * na
     rm2, rmv, rma = (nmm, nF, 0), (nv, nF, nmm), (na, nF, nmm + nv)
     cv, ca = t['cv'], t['ca']
-    if gb is None:
-        gb = to_bf16(g)
-    dz = lin_bwd(fb.mlp.fc2, gb, t['u'], B * nF, gelu_aux=t['z'])
-    g1 = _e((B, nF, D), F32, dev)                 # gradient at xmm1 = residual-path gradient of the normed xmm
-    g1b = _e((B * nF, D), BF16, dev)
     if t.get('ln_fused', False):
+        if gb is None:
+            gb = to_bf16(g)
+        dz = lin_bwd(fb.mlp.fc2, gb, t['u'], B * nF, gelu_aux=t['z'])
+        g1 = _e((B, nF, D), F32, dev)
+        g1b = _e((B * nF, D), BF16, dev)
         dh2 = lin_bwd(fb.mlp.fc1, dz, None, B * nF, wgrad=False)
         h2 = _e((B * nF, D), BF16, dev)
         ln_bwd_tw(fb.norm2, fb.norm2.eps, None, 0, t['tw1'], nF, B, dy_bf16=dh2, h_out=h2, dx1=g1, res1=g, dx1_bf16=g1b)
         lin_wgrad(fb.mlp.fc1, dz, h2, B * nF)
-    else:
-        dh2 = lin_bwd(fb.mlp.fc1, dz, t['h2'], B * nF)
-        ln_bwd(fb.norm2, None, t['xmm1'], B, t['st2'], dy_bf16=dh2, dx1=g1, res1=g, dx1_bf16=g1b)
+    else:       # g1: gradient at xmm1 = residual-path gradient of the normed xmm
+        g1, g1b = _mlp_tail_bwd(fb, t, g, gb, B, nF, D, dev, g1_first=True)
     # d(normed xmm) from the three projections of its row groups lands in one bf16 buffer
     dxmm_b = _e((B * nF, D), BF16, dev)
     # --- pair attention branch (rows [0, nmm)) ---
     do2 = lin_bwd(at.proj, g1b, t['o2'], B * nmm, dy_rowmap=rm2)                                  # [B*nmm, D]
     dq2, dKp, dVp = _e((B * nmm, Da), BF16, dev), _e((B * P, Da), BF16, dev), _e((B * P, D), BF16, dev)
-    attention_bwd((t['q2'], 0), (t['Kp'], 0), (t['Vp'], 0), t['o2'], do2, t['lse2'], (dq2, 0), (dKp, 0), (dVp, 0),
-                  B, heads, nmm, P, Da // heads, hd, hd ** -0.5, nmm * Da, Da, P * Da, Da, P * D, D,
-                  nmm * Da, Da, P * Da, Da, P * D, D)
+    attention_bwd(cols(t['q2'], nmm), cols(t['Kp'], P), cols(t['Vp'], P), t['o2'], do2, t['lse2'],
+                  cols(dq2, nmm), cols(dKp, P), cols(dVp, P), B, heads, nmm, P, Da // heads, hd, hd ** -0.5)
     dkv_p, dka_p = _e((B * nv, Da), BF16, dev), _e((B * na, Da), BF16, dev)
     dvv_p, dva_p = _e((B * nv, D), BF16, dev), _e((B * na, D), BF16, dev)
     with region():
@@ -1201,12 +1288,10 @@ def _factorized_bwd_cross(fb, t, g1, dov, doa, dxmm_b, dx_i, dx_a):
            and ops.attn_bwd_onepass_fits(nv, nI, hd, hd) and ops.attn_bwd_onepass_fits(na, nA, hd, hd))
     for part in ((3,) if one else (1, 2)):
         with region():
-            attention_bwd((cv['q'], 0), (cv['kv'], 0), (cv['kv'], D), cv['o'], dov, cv['lse'], (dq_v, 0), (dkv_v, 0), (dkv_v, D),
-                          B, heads, nv, nI, hd, hd, hd ** -0.5, nv * D, D, nI * 2 * D, 2 * D, nI * 2 * D, 2 * D,
-                          nv * D, D, nI * 2 * D, 2 * D, nI * 2 * D, 2 * D, part=part, Delta=del_v)
-            attention_bwd((ca['q'], 0), (ca['kv'], 0), (ca['kv'], D), ca['o'], doa, ca['lse'], (dq_a, 0), (dkv_a, 0), (dkv_a, D),
-                          B, heads, na, nA, hd, hd, hd ** -0.5, na * D, D, nA * 2 * D, 2 * D, nA * 2 * D, 2 * D,
-                          na * D, D, nA * 2 * D, 2 * D, nA * 2 * D, 2 * D, part=part, Delta=del_a)
+            attention_bwd(cols(cv['q'], nv), cols(cv['kv'], nI), cols(cv['kv'], nI, D), cv['o'], dov, cv['lse'],
+                          cols(dq_v, nv), cols(dkv_v, nI), cols(dkv_v, nI, D), B, heads, nv, nI, hd, hd, hd ** -0.5, part=part, Delta=del_v)
+            attention_bwd(cols(ca['q'], na), cols(ca['kv'], nA), cols(ca['kv'], nA, D), ca['o'], doa, ca['lse'],
+                          cols(dq_a, na), cols(dkv_a, nA), cols(dkv_a, nA, D), B, heads, na, nA, hd, hd, hd ** -0.5, part=part, Delta=del_a)
     fused = t.get('ln_fused', False)
     with region():
         lin_bwd(at.attn_v.q, dq_v, t['xmm_b'], B * nv, a_rowmap=rmv, dx=dxmm_b, dx_rowmap=rmv)
@@ -1214,24 +1299,23 @@ def _factorized_bwd_cross(fb, t, g1, dov, doa, dxmm_b, dx_i, dx_a):
         dxv_b = lin_bwd(at.attn_v.kv, dkv_v, t['xv_b'], B * nI, wgrad=not fused)
         dxa_b = lin_bwd(at.attn_a.kv, dkv_a, t['xa_b'], B * nA, wgrad=not fused)
     # --- the three input LayerNorms ---
+    if not fused:
+        with region():
+            return _input_norms_bwd(fb, t, (fb.norm1_img, x_i, t['st_v'], dxv_b), (fb.norm1_aud, x_a, t['st_a'], dxa_b), dxmm_b, g1,
+                                    dx_i, dx_a, dx_f_first=True)
     acc_i, acc_a = (1 if dx_i is not None else 0), (1 if dx_a is not None else 0)
     if dx_i is None:
         dx_i = _e((B, nI, D), F32, dev)
     if dx_a is None:
         dx_a = _e((B, nA, D), F32, dev)
     dx_f = _e((B, nF, D), F32, dev)
-    with region():
-        if fused:      # (folded on the forward path: the backward re-makes the kv projections' weight-gradient operands)
-            hv, ha = _e((B * nI, D), BF16, dev), _e((B * nA, D), BF16, dev)
-            ln_bwd_tw(fb.norm1_img, fb.norm1_img.eps, None, 0, t['ti'], nI, B, dy_bf16=dxv_b, h_out=hv, dx1=dx_i, acc1=acc_i)
-            ln_bwd_tw(fb.norm1_aud, fb.norm1_aud.eps, None, 0, t['ta'], nA, B, dy_bf16=dxa_b, h_out=ha, dx1=dx_a, acc1=acc_a)
-        else:
-            ln_bwd(fb.norm1_img, None, x_i, B, t['st_v'], dy_bf16=dxv_b, dx1=dx_i, acc1=acc_i)
-            ln_bwd(fb.norm1_aud, None, x_a, B, t['st_a'], dy_bf16=dxa_b, dx1=dx_a, acc1=acc_a)
+    with region():      # (folded on the forward path: the backward re-makes the kv projections' weight-gradient operands)
+        hv, ha = _e((B * nI, D), BF16, dev), _e((B * nA, D), BF16, dev)
+        ln_bwd_tw(fb.norm1_img, fb.norm1_img.eps, None, 0, t['ti'], nI, B, dy_bf16=dxv_b, h_out=hv, dx1=dx_i, acc1=acc_i)
+        ln_bwd_tw(fb.norm1_aud, fb.norm1_aud.eps, None, 0, t['ta'], nA, B, dy_bf16=dxa_b, h_out=ha, dx1=dx_a, acc1=acc_a)
         ln_bwd(fb.norm1_mm, None, x_f, B, t['st_mm'], dy_bf16=dxmm_b, dy_f32=g1, dx1=dx_f)
-    if fused:
-        lin_wgrad(at.attn_v.kv, dkv_v, hv, B * nI)
-        lin_wgrad(at.attn_a.kv, dkv_a, ha, B * nA)
+    lin_wgrad(at.attn_v.kv, dkv_v, hv, B * nI)
+    lin_wgrad(at.attn_a.kv, dkv_a, ha, B * nA)
     return dx_f, dx_i, dx_a
 
 
@@ -1242,8 +1326,7 @@ def _cross_fwd_seq(ca, xq_b, q_rowmap, nq, xkv_b, nk, B, D, heads, dev, keep=Non
     hd = D // heads
     q = lin_fwd(ca.q, xq_b, B * nq, a_rowmap=q_rowmap, out_bf16=True)                        # [B*nq, D]
     kv = lin_fwd(ca.kv, xkv_b, B * nk, out_bf16=True)                                        # [B*nk, 2D]
-    o, lse = attention_fwd((q, 0), (kv, 0), (kv, D), B, heads, nq, nk, hd, hd, hd ** -0.5,
-                           nq * D, D, nk * 2 * D, 2 * D, nk * 2 * D, 2 * D, dev, keep=keep)
+    o, lse = attention_fwd(cols(q, nq), cols(kv, nk), cols(kv, nk, D), B, heads, nq, nk, hd, hd, hd ** -0.5, keep=keep)
     return dict(q=q, kv=kv, o=o, lse=lse, keep=keep)
 
 
@@ -1253,9 +1336,8 @@ def _cross_bwd_seq(ca, c, do, xq_b, q_rowmap, nq, xkv_b, nk, B, D, heads, dxq_ou
     hd, dev = D // heads, do.device
     dq = _e((B * nq, D), BF16, dev)
     dkv = _e((B * nk, 2 * D), BF16, dev)
-    attention_bwd((c['q'], 0), (c['kv'], 0), (c['kv'], D), c['o'], do, c['lse'], (dq, 0), (dkv, 0), (dkv, D),
-                  B, heads, nq, nk, hd, hd, hd ** -0.5, nq * D, D, nk * 2 * D, 2 * D, nk * 2 * D, 2 * D,
-                  nq * D, D, nk * 2 * D, 2 * D, nk * 2 * D, 2 * D, keep=c.get('keep'))
+    attention_bwd(cols(c['q'], nq), cols(c['kv'], nk), cols(c['kv'], nk, D), c['o'], do, c['lse'],
+                  cols(dq, nq), cols(dkv, nk), cols(dkv, nk, D), B, heads, nq, nk, hd, hd, hd ** -0.5, keep=c.get('keep'))
     lin_bwd(ca.q, dq, xq_b, B * nq, a_rowmap=q_rowmap, dx=dxq_out, dx_rowmap=dxq_rowmap)
     return lin_bwd(ca.kv, dkv, xkv_b, B * nk)
 
@@ -1302,8 +1384,8 @@ def _factorized_fwd_seq(fb, x_f, x_i, x_a, heads, tkns, dp=None, dr=None):
     ops.pair_expand(vv_p, va_p, B, nv, na, D, Vp)
     q2 = lin_fwd(at.q, xmm_b, B * nmm, a_rowmap=rm2, out_bf16=True)                          # [B*nmm, Da]
     scale = (D // heads) ** -0.5                                                             # NOT (Da/heads)^-0.5 (:220-222)
-    o2, lse2 = attention_fwd((q2, 0), (Kp, 0), (Vp, 0), B, heads, nmm, P, Da // heads, D // heads, scale,
-                             nmm * Da, Da, P * Da, Da, P * D, D, dev, keep=dr.get('attn'))
+    o2, lse2 = attention_fwd(cols(q2, nmm), cols(Kp, P), cols(Vp, P), B, heads, nmm, P, Da // heads, D // heads, scale,
+                             keep=dr.get('attn'))
     lin_fwd(at.proj, o2, B * nmm, res=r32, res_rowmap=rm2, out=xmm1, c_rowmap=rm2)
     keep_rows = None
     if any(m is not None for m in pdrop):
@@ -1315,16 +1397,9 @@ def _factorized_fwd_seq(fb, x_f, x_i, x_a, heads, tkns, dp=None, dr=None):
         ops.dropout_rows(xmm1, keep_rows[0], ks, B, nF, D, xmm1, res=xmm32, rowscale=None if dp is None else dp[0])
     elif dp is not None:
         ops.rows_axpy(xmm32, xmm1, dp[0], B, nF, D, xmm1)               # xmm + s[b] * attn(xmm, xv, xa)
-    h2, _, st2 = ln_fwd(fb.norm2, None, xmm1, B)
-    Hd = fb.mlp.fc1.weight.shape[0]
-    z = _e((B * nF, Hd), BF16, dev)
-    u = lin_fwd(fb.mlp.fc1, h2, B * nF, act=1, out_bf16=True, C2=z, c2_mode=4)
-    if 'fc1' in dr:
-        _drop(u, dr['fc1'], B, nF, Hd)
-    out = _res_add(fb.mlp.fc2, u, B * nF, xmm1, B, nF, D, None if dp is None else dp[1], drop=dr.get('fc2')).view(B, nF, D)
-    tape = dict(dp=dp, dr=dr or None, keep_rows=keep_rows, x_f=x_f, x_i=x_i, x_a=x_a, xmm_b=xmm_b, st_mm=st_mm, xv_b=xv_b, st_v=st_v, xa_b=xa_b, st_a=st_a, cv=cv, ca=ca,
-                xvo_b=xvo_b, xao_b=xao_b, Kp=Kp, Vp=Vp, q2=q2, o2=o2, lse2=lse2, xmm1=xmm1, h2=h2, st2=st2, z=z, u=u,
-                heads=heads, tkns=tkns)
+    out, tt = _mlp_tail_fwd(fb, xmm1, B, nF, D, dev, dp, dr)
+    tape = dict(tt, keep_rows=keep_rows, x_f=x_f, x_i=x_i, x_a=x_a, xmm_b=xmm_b, st_mm=st_mm, xv_b=xv_b, st_v=st_v, xa_b=xa_b, st_a=st_a,
+                cv=cv, ca=ca, xvo_b=xvo_b, xao_b=xao_b, Kp=Kp, Vp=Vp, q2=q2, o2=o2, lse2=lse2, heads=heads, tkns=tkns)
     return out, tape
 
 
@@ -1341,17 +1416,7 @@ def _factorized_bwd_seq(fb, t, g, gb, *, dx_i=None, dx_a=None):
     rm2, rmv, rma = (nmm, nF, 0), (nv, nF, nmm), (na, nF, nmm + nv)
     dp = t.get('dp')
     dr = t.get('dr') or {}
-    if dp is not None or 'fc2' in dr:
-        gb = _branch_grad(g, None if dp is None else dp[1], dr.get('fc2'), B, nF, D)
-    elif gb is None:
-        gb = to_bf16(g)
-    dz = lin_bwd(fb.mlp.fc2, gb, t['u'], B * nF, gelu_aux=t['z'])
-    if 'fc1' in dr:
-        _drop(dz, dr['fc1'], B, nF, dz.shape[1])
-    dh2 = lin_bwd(fb.mlp.fc1, dz, t['h2'], B * nF)
-    g1 = _e((B, nF, D), F32, dev)
-    g1b = _e((B * nF, D), BF16, dev)
-    ln_bwd(fb.norm2, None, t['xmm1'], B, t['st2'], dy_bf16=dh2, dx1=g1, res1=g, dx1_bf16=g1b)
+    g1, g1b = _mlp_tail_bwd(fb, t, g, gb, B, nF, D, dev)
     # g1 = gradient at xmm1: unchanged it is the residual-path gradient of the normed xmm (norm1_mm backward below);
     # the attention branch sees it scaled per sample when DropPath is on, and masked where its projections were dropped:
     #   gy   gradient of the branch output cat((xmm2, xmm_v, xmm_a)) AFTER the dropouts (what the pairs' gradients add to),
@@ -1368,9 +1433,9 @@ def _factorized_bwd_seq(fb, t, g, gb, *, dx_i=None, dx_a=None):
     # --- pair attention branch (rows [0, nmm)) ---
     do2 = lin_bwd(at.proj, g1b, t['o2'], B * nmm, dy_rowmap=rm2)                              # [B*nmm, D]
     dq2, dKp, dVp = _e((B * nmm, Da), BF16, dev), _e((B * P, Da), BF16, dev), _e((B * P, D), BF16, dev)
-    attention_bwd((t['q2'], 0), (t['Kp'], 0), (t['Vp'], 0), t['o2'], do2, t['lse2'], (dq2, 0), (dKp, 0), (dVp, 0),
-                  B, heads, nmm, P, Da // heads, D // heads, (D // heads) ** -0.5, nmm * Da, Da, P * Da, Da, P * D, D,
-                  nmm * Da, Da, P * Da, Da, P * D, D, keep=dr.get('attn'))
+    attention_bwd(cols(t['q2'], nmm), cols(t['Kp'], P), cols(t['Vp'], P), t['o2'], do2, t['lse2'],
+                  cols(dq2, nmm), cols(dKp, P), cols(dVp, P), B, heads, nmm, P, Da // heads, D // heads, (D // heads) ** -0.5,
+                  keep=dr.get('attn'))
     lin_bwd(at.q, dq2, t['xmm_b'], B * nmm, a_rowmap=rm2, dx=dxmm_b, dx_rowmap=rm2)
     dkv_p, dka_p = _e((B * nv, Da), BF16, dev), _e((B * na, Da), BF16, dev)
     dvv_p, dva_p = _e((B * nv, D), BF16, dev), _e((B * na, D), BF16, dev)
@@ -1397,16 +1462,7 @@ def _factorized_bwd_seq(fb, t, g, gb, *, dx_i=None, dx_a=None):
     dxv_b = _cross_bwd_seq(at.attn_v, t['cv'], dov, t['xmm_b'], rmv, nv, t['xv_b'], nI, B, D, heads, dxmm_b, rmv)
     dxa_b = _cross_bwd_seq(at.attn_a, t['ca'], doa, t['xmm_b'], rma, na, t['xa_b'], nA, B, D, heads, dxmm_b, rma)
     # --- the three input LayerNorms ---
-    acc_i, acc_a = (1 if dx_i is not None else 0), (1 if dx_a is not None else 0)
-    if dx_i is None:
-        dx_i = _e((B, nI, D), F32, dev)
-    if dx_a is None:
-        dx_a = _e((B, nA, D), F32, dev)
-    ln_bwd(fb.norm1_img, None, x_i, B, t['st_v'], dy_bf16=dxv_b, dx1=dx_i, acc1=acc_i)
-    ln_bwd(fb.norm1_aud, None, x_a, B, t['st_a'], dy_bf16=dxa_b, dx1=dx_a, acc1=acc_a)
-    dx_f = _e((B, nF, D), F32, dev)
-    ln_bwd(fb.norm1_mm, None, x_f, B, t['st_mm'], dy_bf16=dxmm_b, dy_f32=g1, dx1=dx_f)
-    return dx_f, dx_i, dx_a
+    return _input_norms_bwd(fb, t, (fb.norm1_img, x_i, t['st_v'], dxv_b), (fb.norm1_aud, x_a, t['st_a'], dxa_b), dxmm_b, g1, dx_i, dx_a)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1415,41 +1471,8 @@ def _factorized_bwd_seq(fb, t, g, gb, *, dx_i=None, dx_a=None):
 # parameter names are reproduced:
 #   token     : norm1_img normalises the 3rd argument (audio), norm1_aud the 2nd (image); keys = [audio rows | image rows]
 #   dense_mmi : norms in order; inside the attention pairs are (audio_i, image_j), p = i*nI + j, features [audio || image]
-# Both share the norm-then-residual form and the norm2 + MLP tail of the factorised block.
+# Both share the norm-then-residual form and the norm2 + MLP tail of the factorised block (_mlp_tail_fwd / _mlp_tail_bwd).
 # ------------------------------------------------------------------------------------------------
-def _alt_tail_fwd(fb, xmm1, B, nF, D, dev, dp=None, dr=None):
-    dr = dr or {}
-    h2, _, st2 = ln_fwd(fb.norm2, None, xmm1, B)
-    Hd = fb.mlp.fc1.weight.shape[0]
-    z = _e((B * nF, Hd), BF16, dev)
-    u = lin_fwd(fb.mlp.fc1, h2, B * nF, act=1, out_bf16=True, C2=z, c2_mode=4)
-    if 'fc1' in dr:
-        _drop(u, dr['fc1'], B, nF, Hd)
-    out = _res_add(fb.mlp.fc2, u, B * nF, xmm1, B, nF, D, None if dp is None else dp[1], drop=dr.get('fc2')).view(B, nF, D)
-    return out, dict(h2=h2, st2=st2, z=z, u=u, xmm1=xmm1, dp=dp, dr=dr or None)
-
-
-def _alt_tail_bwd(fb, tt, g, gb, B, nF, D, dev):
-    """-> (g1 fp32 [B,nF,D], g1b bf16): gradient at xmm1 (the attention residual output); with DropPath g1b is the
-    gradient of the attention BRANCH (scaled per sample), g1 stays the residual-path gradient."""
-    dp = tt.get('dp')
-    dr = tt.get('dr') or {}
-    if dp is not None or 'fc2' in dr:
-        gb = _branch_grad(g, None if dp is None else dp[1], dr.get('fc2'), B, nF, D)
-    elif gb is None:
-        gb = to_bf16(g)
-    dz = lin_bwd(fb.mlp.fc2, gb, tt['u'], B * nF, gelu_aux=tt['z'])
-    if 'fc1' in dr:
-        _drop(dz, dr['fc1'], B, nF, dz.shape[1])
-    dh2 = lin_bwd(fb.mlp.fc1, dz, tt['h2'], B * nF)
-    g1 = _e((B, nF, D), F32, dev)
-    g1b = _e((B * nF, D), BF16, dev)
-    ln_bwd(fb.norm2, None, tt['xmm1'], B, tt['st2'], dy_bf16=dh2, dx1=g1, res1=g, dx1_bf16=g1b)
-    if dp is not None or 'proj' in dr:
-        g1b = _branch_grad(g1, None if dp is None else dp[0], dr.get('proj'), B, nF, D)
-    return g1, g1b
-
-
 def _token_fwd(fb, x_f, x_2, x_3, heads, dp=None, dr=None):
     dr = dr or {}
     B, nF, D = x_f.shape
@@ -1465,10 +1488,9 @@ def _token_fwd(fb, x_f, x_2, x_3, heads, dp=None, dr=None):
     lin_fwd(at.kv, x3_b, B * n3, out=kv, c_rowmap=(n3, nS, 0))
     lin_fwd(at.kv, x2_b, B * n2, out=kv, c_rowmap=(n2, nS, n3))
     q = lin_fwd(at.q, xmm_b, B * nF, out_bf16=True)
-    o, lse = attention_fwd((q, 0), (kv, 0), (kv, Da), B, heads, nF, nS, hd, hd, hd ** -0.5,
-                           nF * Da, Da, nS * 2 * Da, 2 * Da, nS * 2 * Da, 2 * Da, dev, keep=dr.get('attn'))
+    o, lse = attention_fwd(cols(q, nF), cols(kv, nS), cols(kv, nS, Da), B, heads, nF, nS, hd, hd, hd ** -0.5, keep=dr.get('attn'))
     xmm1 = _res_add(at.proj, o, B * nF, xmm32, B, nF, D, None if dp is None else dp[0], drop=dr.get('proj')).view(B, nF, D)
-    out, tt = _alt_tail_fwd(fb, xmm1, B, nF, D, dev, dp, dr)
+    out, tt = _mlp_tail_fwd(fb, xmm1, B, nF, D, dev, dp, dr)
     tt.update(arch='token', x_f=x_f, x_2=x_2, x_3=x_3, xmm_b=xmm_b, st_mm=st_mm, x2_b=x2_b, st_2=st_2, x3_b=x3_b, st_3=st_3,
               kv=kv, q=q, o=o, lse=lse, heads=heads)
     return out, tt
@@ -1482,25 +1504,19 @@ def _token_bwd(fb, t, g, gb, *, dx_i=None, dx_a=None):
     dev, at = x_f.device, fb.attn
     Da = at.q.weight.shape[0]
     hd = Da // heads
-    g1, g1b = _alt_tail_bwd(fb, t, g, gb, B, nF, D, dev)
+    g1, g1b = _mlp_tail_bwd(fb, t, g, gb, B, nF, D, dev)
+    dp, dr = t.get('dp'), t.get('dr') or {}
+    if dp is not None or 'proj' in dr:      # g1b -> the gradient of the attention BRANCH (scaled per sample, masked)
+        g1b = _branch_grad(g1, None if dp is None else dp[0], dr.get('proj'), B, nF, D)
     do = lin_bwd(at.proj, g1b, t['o'], B * nF)
     dq, dkv = _e((B * nF, Da), BF16, dev), _e((B * nS, 2 * Da), BF16, dev)
-    attention_bwd((t['q'], 0), (t['kv'], 0), (t['kv'], Da), t['o'], do, t['lse'], (dq, 0), (dkv, 0), (dkv, Da),
-                  B, heads, nF, nS, hd, hd, hd ** -0.5, nF * Da, Da, nS * 2 * Da, 2 * Da, nS * 2 * Da, 2 * Da,
-                  nF * Da, Da, nS * 2 * Da, 2 * Da, nS * 2 * Da, 2 * Da, keep=(t.get('dr') or {}).get('attn'))
+    attention_bwd(cols(t['q'], nF), cols(t['kv'], nS), cols(t['kv'], nS, Da), t['o'], do, t['lse'],
+                  cols(dq, nF), cols(dkv, nS), cols(dkv, nS, Da), B, heads, nF, nS, hd, hd, hd ** -0.5, keep=dr.get('attn'))
     dxmm_b = lin_bwd(at.q, dq, t['xmm_b'], B * nF)
     dx3_b = lin_bwd(at.kv, dkv, t['x3_b'], B * n3, dy_rowmap=(n3, nS, 0), final=False)
     dx2_b = lin_bwd(at.kv, dkv, t['x2_b'], B * n2, dy_rowmap=(n2, nS, n3))
-    acc_2, acc_3 = (1 if dx_i is not None else 0), (1 if dx_a is not None else 0)
-    if dx_i is None:
-        dx_i = _e((B, n2, D), F32, dev)
-    if dx_a is None:
-        dx_a = _e((B, n3, D), F32, dev)
-    ln_bwd(fb.norm1_aud, None, x_2, B, t['st_2'], dy_bf16=dx2_b, dx1=dx_i, acc1=acc_2)
-    ln_bwd(fb.norm1_img, None, x_3, B, t['st_3'], dy_bf16=dx3_b, dx1=dx_a, acc1=acc_3)
-    dx_f = _e((B, nF, D), F32, dev)
-    ln_bwd(fb.norm1_mm, None, x_f, B, t['st_mm'], dy_bf16=dxmm_b, dy_f32=g1, dx1=dx_f)
-    return dx_f, dx_i, dx_a
+    # (the reference's swapped names: norm1_aud on the 2nd argument -> dx_i first, then norm1_img on the 3rd -> dx_a)
+    return _input_norms_bwd(fb, t, (fb.norm1_aud, x_2, t['st_2'], dx2_b), (fb.norm1_img, x_3, t['st_3'], dx3_b), dxmm_b, g1, dx_i, dx_a)
 
 
 def _dense_fwd(fb, x_f, x_i, x_a, heads, dp=None, dr=None):
@@ -1522,10 +1538,9 @@ def _dense_fwd(fb, x_f, x_i, x_a, heads, dp=None, dr=None):
     ops.pair_expand(pa, pi, B, nA, nI, 2 * Da, KV)
     q = lin_fwd(at.q, xmm_b, B * nF, out_bf16=True)
     scale = (D // heads) ** -0.5                                  # from the FULL dim (:157-158)
-    o, lse = attention_fwd((q, 0), (KV, 0), (KV, Da), B, heads, nF, P, hd, hd, scale,
-                           nF * Da, Da, P * 2 * Da, 2 * Da, P * 2 * Da, 2 * Da, dev, keep=dr.get('attn'))
+    o, lse = attention_fwd(cols(q, nF), cols(KV, P), cols(KV, P, Da), B, heads, nF, P, hd, hd, scale, keep=dr.get('attn'))
     xmm1 = _res_add(at.proj, o, B * nF, xmm32, B, nF, D, None if dp is None else dp[0], drop=dr.get('proj')).view(B, nF, D)
-    out, tt = _alt_tail_fwd(fb, xmm1, B, nF, D, dev, dp, dr)
+    out, tt = _mlp_tail_fwd(fb, xmm1, B, nF, D, dev, dp, dr)
     tt.update(arch='dense_mmi', x_f=x_f, x_i=x_i, x_a=x_a, xmm_b=xmm_b, st_mm=st_mm, xi_b=xi_b, st_i=st_i, xa_b=xa_b, st_a=st_a,
               KV=KV, q=q, o=o, lse=lse, heads=heads)
     return out, tt
@@ -1539,28 +1554,21 @@ def _dense_bwd(fb, t, g, gb, *, dx_i=None, dx_a=None):
     dev, at = x_f.device, fb.attn
     Da = at.q.weight.shape[0]
     hd = Da // heads
-    g1, g1b = _alt_tail_bwd(fb, t, g, gb, B, nF, D, dev)
+    g1, g1b = _mlp_tail_bwd(fb, t, g, gb, B, nF, D, dev)
+    dp, dr = t.get('dp'), t.get('dr') or {}
+    if dp is not None or 'proj' in dr:      # g1b -> the gradient of the attention BRANCH (scaled per sample, masked)
+        g1b = _branch_grad(g1, None if dp is None else dp[0], dr.get('proj'), B, nF, D)
     do = lin_bwd(at.proj, g1b, t['o'], B * nF)
     dq, dKV = _e((B * nF, Da), BF16, dev), _e((B * P, 2 * Da), BF16, dev)
     scale = (D // heads) ** -0.5
-    attention_bwd((t['q'], 0), (t['KV'], 0), (t['KV'], Da), t['o'], do, t['lse'], (dq, 0), (dKV, 0), (dKV, Da),
-                  B, heads, nF, P, hd, hd, scale, nF * Da, Da, P * 2 * Da, 2 * Da, P * 2 * Da, 2 * Da,
-                  nF * Da, Da, P * 2 * Da, 2 * Da, P * 2 * Da, 2 * Da, keep=(t.get('dr') or {}).get('attn'))
+    attention_bwd(cols(t['q'], nF), cols(t['KV'], P), cols(t['KV'], P, Da), t['o'], do, t['lse'],
+                  cols(dq, nF), cols(dKV, P), cols(dKV, P, Da), B, heads, nF, P, hd, hd, scale, keep=dr.get('attn'))
     dxmm_b = lin_bwd(at.q, dq, t['xmm_b'], B * nF)
     dpa, dpi = _e((B * nA, 2 * Da), BF16, dev), _e((B * nI, 2 * Da), BF16, dev)
     ops.pair_reduce(dKV, B, nA, nI, 2 * Da, dpa, dpi)
     dxa_b = lin_bwd(at.kv, dpa, t['xa_b'], B * nA, k=D, final=False)
     dxi_b = lin_bwd(at.kv, dpi, t['xi_b'], B * nI, k=D, w_col_off=D, use_bias=False)
-    acc_i, acc_a = (1 if dx_i is not None else 0), (1 if dx_a is not None else 0)
-    if dx_i is None:
-        dx_i = _e((B, nI, D), F32, dev)
-    if dx_a is None:
-        dx_a = _e((B, nA, D), F32, dev)
-    ln_bwd(fb.norm1_img, None, x_i, B, t['st_i'], dy_bf16=dxi_b, dx1=dx_i, acc1=acc_i)
-    ln_bwd(fb.norm1_aud, None, x_a, B, t['st_a'], dy_bf16=dxa_b, dx1=dx_a, acc1=acc_a)
-    dx_f = _e((B, nF, D), F32, dev)
-    ln_bwd(fb.norm1_mm, None, x_f, B, t['st_mm'], dy_bf16=dxmm_b, dy_f32=g1, dx1=dx_f)
-    return dx_f, dx_i, dx_a
+    return _input_norms_bwd(fb, t, (fb.norm1_img, x_i, t['st_i'], dxi_b), (fb.norm1_aud, x_a, t['st_a'], dxa_b), dxmm_b, g1, dx_i, dx_a)
 
 
 # steps a tower block idles when it runs as a lane beside the factorised fusion block (see _factorized_fwd / _bwd):
@@ -1779,12 +1787,7 @@ def swin_block_fwd(blk, x, nF):
     bias = _e((nb, heads, N, ld), F32, dev)                                                # rebuilt per step: the table is a parameter
     ops.relpos_bias_build(blk.attn.relative_position_bias_table, blk.index32, blk.attn_mask, nb, heads, A, N, ld,
                           1.0 if PRECISION == 'fp32' else LOG2E, bias)
-    o = _e((Mw, D), BF16, dev)
-    lse = _e((B * nW, heads, N), F32, dev)
-    ops.hold(qkv)
-    es = qkv.element_size()
-    ops.attn_bias_fwd(qkv.data_ptr(), qkv.data_ptr() + es * D, qkv.data_ptr() + es * 2 * D, o, lse, B * nW, heads, N, N, hd, hd,
-                      N * 3 * D, 3 * D, N * 3 * D, 3 * D, N * 3 * D, 3 * D, N * D, D, blk.attn.scale, bias, nb, ld)
+    o, lse = attention_fwd(*qkv_cols(qkv, N, D), B * nW, heads, N, N, hd, hd, blk.attn.scale, bias=(bias, nb, ld))      # o [Mw, D]
     t = lin_fwd(blk.attn.proj, o, Mw)                                                      # fp32 [Mw, D]
     x1 = _e((B, R, D), F32, dev)
     ops.window_fold(t, blk.inv32, x, B, nW, A, nF, L, D, 1.0 / nW, x1)                     # window_reverse + roll back + mean (:191-201)
@@ -1816,13 +1819,8 @@ def swin_block_bwd(blk, t, g2, g2b=None):
     do = lin_bwd(blk.attn.proj, dt, t['o'], Mw)
     dqkv = _e((Mw, 3 * D), BF16, dev)
     dS = _e((B * nW, heads, N, t['ld']), F32, dev)
-    qkv = t['qkv']
-    ops.hold(qkv, dqkv)
-    es = qkv.element_size()
-    ops.attn_bias_bwd(qkv.data_ptr(), qkv.data_ptr() + es * D, qkv.data_ptr() + es * 2 * D, t['o'], do, t['lse'],
-                      torch.empty_like(t['lse']), dqkv.data_ptr(), dqkv.data_ptr() + es * D, dqkv.data_ptr() + es * 2 * D,
-                      B * nW, heads, N, N, hd, hd, N * 3 * D, 3 * D, N * 3 * D, 3 * D, N * 3 * D, 3 * D, N * D, D, N * D, D,
-                      N * 3 * D, 3 * D, N * 3 * D, 3 * D, N * 3 * D, 3 * D, blk.attn.scale, t['bias'], t['nb'], t['ld'], dS)
+    attention_bwd(*qkv_cols(t['qkv'], N, D), t['o'], do, t['lse'], *qkv_cols(dqkv, N, D), B * nW, heads, N, N, hd, hd, blk.attn.scale,
+                  bias=(t['bias'], t['nb'], t['ld']), dS=dS)
     table = blk.attn.relative_position_bias_table
     ops.relpos_bias_bwd(dS, blk.index32, B * nW, heads, A, N, t['ld'], table.shape[0], gbuf(table))
     _ready(table)

@@ -292,35 +292,48 @@ def gemm_tn_gang(problems, workspace_fill=None, gate=None):
     _lib.check(lib.dav_gemm_tn_gang_bf16(arr, len(problems), _ptr(ws), nbytes, _stream()), 'dav_gemm_tn_gang_bf16')
 
 
+def _attn_fwd_call(variant, q_ptr, k_ptr, v_ptr, O, LSE, dims, scale, tail=()):
+    """The argument block all forward attention entry points share.  ``variant`` ('' / '_bias' / '_drop') and the dtype of ``O`` pick
+    the entry point, ``dims`` = (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs), ``tail`` = the variant's own
+    arguments, which follow ``scale`` in the C signature (_lib.SIGNATURES)."""
+    name = 'dav_attn' + variant + '_fwd' + ('_f32' if O.dtype == F32 else '')
+    _lib.check(getattr(_lib.load(), name)(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(LSE), *dims, float(scale), *tail, _stream()), name)
+
+
+def _attn_bwd_call(variant, q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr, dims, scale, part, tail=(), dq_ctx_rows=0):
+    """The backward counterpart: ``dims`` = (B, H, Nq, Nk, dqk, dv) + the (batch, row) strides of q, k, v, O, dO, dq, dk, dv.  C order
+    behind ``scale``: the variant's ``tail``, the context-row count (dav_attn_bwd_ctx and dav_attn_drop_bwd only), ``part``.  The
+    callers refuse ``dq_ctx_rows`` on the fp32 path, which has no such entry."""
+    f32 = O.dtype == F32
+    if variant == '':
+        entry = 'dav_attn_bwd_f32' if f32 else ('dav_attn_bwd_ctx' if dq_ctx_rows else 'dav_attn_bwd_part')
+    else:
+        entry = 'dav_attn' + variant + '_bwd' + ('_f32' if f32 else '')
+    ctx = (int(dq_ctx_rows),) if entry in ('dav_attn_bwd_ctx', 'dav_attn_drop_bwd') else ()
+    _lib.check(getattr(_lib.load(), entry)(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr, *dims,
+                                           float(scale), *tail, *ctx, part, _stream()),
+               'dav_attn_bwd' if entry == 'dav_attn_bwd_part' else entry)
+
+
 def attn_fwd(q_ptr, k_ptr, v_ptr, O, LSE, B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, scale):
     """q / k / v are raw addresses (views into fused projection buffers) of the dtype of ``O``."""
-    lib = _lib.load()
-    if O.dtype == F32:
-        _lib.check(lib.dav_attn_fwd_f32(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(LSE), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
-                                        v_bs, v_rs, o_bs, o_rs, float(scale), _stream()), 'dav_attn_fwd_f32')
-        return
-    _lib.check(lib.dav_attn_fwd(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(LSE), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
-                                v_bs, v_rs, o_bs, o_rs, float(scale), _stream()), 'dav_attn_fwd')
+    _attn_fwd_call('', q_ptr, k_ptr, v_ptr, O, LSE, (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs), scale)
 
 
 def attn_bias_fwd(q_ptr, k_ptr, v_ptr, O, LSE, B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, scale,
                   bias, bias_nb, bias_ld):
     """attn_fwd with an additive logit bias [bias_nb, H, Nq, bias_ld] (bf16 path: log2 units; fp32 path: natural units)."""
-    lib = _lib.load()
-    fn, name = (lib.dav_attn_bias_fwd_f32, 'dav_attn_bias_fwd_f32') if O.dtype == F32 else (lib.dav_attn_bias_fwd, 'dav_attn_bias_fwd')
-    _lib.check(fn(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(LSE), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs,
-                  float(scale), _ptr(bias), bias_nb, bias_ld, _stream()), name)
+    _attn_fwd_call('_bias', q_ptr, k_ptr, v_ptr, O, LSE, (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs), scale,
+                   (_ptr(bias), bias_nb, bias_ld))
 
 
 def attn_bias_bwd(q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr, B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
                   v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, scale, bias, bias_nb, bias_ld,
                   dS, part=3):
     """attn_bwd with the bias of the forward; dS [B, H, Nq, bias_ld] fp32 receives the gradient of the biased logits."""
-    lib = _lib.load()
-    fn, name = (lib.dav_attn_bias_bwd_f32, 'dav_attn_bias_bwd_f32') if O.dtype == F32 else (lib.dav_attn_bias_bwd, 'dav_attn_bias_bwd')
-    _lib.check(fn(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr, B, H, Nq, Nk, dqk, dv,
-                  q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs,
-                  float(scale), _ptr(bias), bias_nb, bias_ld, _ptr(dS), part, _stream()), name)
+    _attn_bwd_call('_bias', q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr,
+                   (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs,
+                    dv_bs, dv_rs), scale, part, (_ptr(bias), bias_nb, bias_ld, _ptr(dS)))
 
 
 def window_unfold(src, rows32, B, nW, A, nF, L, Cc, fusion_scale, out):
@@ -349,22 +362,11 @@ def attn_bwd(q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr, B, 
              v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, scale, part=3, dq_ctx_rows=0):
     """part 1: dQ (+ Delta) kernel only, 2: dK/dV kernel only (after part 1), 3: both.  dq_ctx_rows (bf16 path): rows in front of
     the first query row of every batch element of the dQ buffer whose dqk columns the dQ kernel zero-fills (dav_attn_bwd_ctx)."""
-    lib = _lib.load()
-    if O.dtype == F32:
-        if dq_ctx_rows:
-            raise RuntimeError('dq_ctx_rows: bf16 path only')
-        _lib.check(lib.dav_attn_bwd_f32(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr,
-                                        B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs,
-                                        dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), part, _stream()), 'dav_attn_bwd_f32')
-        return
-    if dq_ctx_rows:
-        _lib.check(lib.dav_attn_bwd_ctx(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr,
-                                        B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs,
-                                        dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), int(dq_ctx_rows), part, _stream()), 'dav_attn_bwd_ctx')
-        return
-    _lib.check(lib.dav_attn_bwd_part(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr,
-                                     B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs,
-                                     dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), part, _stream()), 'dav_attn_bwd')
+    if O.dtype == F32 and dq_ctx_rows:
+        raise RuntimeError('dq_ctx_rows: bf16 path only')
+    _attn_bwd_call('', q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr,
+                   (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs,
+                    dv_bs, dv_rs), scale, part, dq_ctx_rows=dq_ctx_rows)
 
 
 ATTN_RESIDENT_MAX = 80 * 1024      # csrc/attention.hip: LDS of a resident attention workgroup (two per CU)
@@ -588,28 +590,18 @@ def rows_scale_cast(g, scale, B, rows, D, out_bf16):
 def attn_drop_fwd(q_ptr, k_ptr, v_ptr, O, LSE, B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, scale,
                   keep, keep_ld, keep_scale):
     """Attention with dropout on the softmax probabilities (dav_attn_drop_fwd / _f32): keep = bytes 0 / 1 [B, H, Nq, keep_ld]."""
-    lib = _lib.load()
-    fn, name = (lib.dav_attn_drop_fwd_f32, 'dav_attn_drop_fwd_f32') if O.dtype == F32 else (lib.dav_attn_drop_fwd, 'dav_attn_drop_fwd')
-    _lib.check(fn(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(LSE), B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs,
-                  float(scale), _ptr(keep), keep_ld, float(keep_scale), _stream()), name)
+    _attn_fwd_call('_drop', q_ptr, k_ptr, v_ptr, O, LSE, (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs), scale,
+                   (_ptr(keep), keep_ld, float(keep_scale)))
 
 
 def attn_drop_bwd(q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr, B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs,
                   v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, scale, keep, keep_ld, keep_scale,
                   part=3, dq_ctx_rows=0):
-    lib = _lib.load()
-    if O.dtype == F32:
-        if dq_ctx_rows:
-            raise ValueError('the fp32 attention kernels have no context-row entry')
-        _lib.check(lib.dav_attn_drop_bwd_f32(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr,
-                                             B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs,
-                                             dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), _ptr(keep), keep_ld,
-                                             float(keep_scale), part, _stream()), 'dav_attn_drop_bwd_f32')
-        return
-    _lib.check(lib.dav_attn_drop_bwd(q_ptr, k_ptr, v_ptr, _ptr(O), _ptr(dO), _ptr(LSE), _ptr(Delta), dq_ptr, dk_ptr, dv_ptr,
-                                     B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs,
-                                     dq_bs, dq_rs, dk_bs, dk_rs, dv_bs, dv_rs, float(scale), _ptr(keep), keep_ld, float(keep_scale),
-                                     dq_ctx_rows, part, _stream()), 'dav_attn_drop_bwd')
+    if O.dtype == F32 and dq_ctx_rows:
+        raise ValueError('the fp32 attention kernels have no context-row entry')
+    _attn_bwd_call('_drop', q_ptr, k_ptr, v_ptr, O, dO, LSE, Delta, dq_ptr, dk_ptr, dv_ptr,
+                   (B, H, Nq, Nk, dqk, dv, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs, dk_bs, dk_rs,
+                    dv_bs, dv_rs), scale, part, (_ptr(keep), keep_ld, float(keep_scale)), dq_ctx_rows)
 
 
 def dropout_rows(x, keep, keep_scale, B, rows, D, out, res=None, rowscale=None):
