@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised shape fuzz of the C-ABI kernels against torch fp32 references (companion of tests/gpu_selfcheck.py, which uses
-fixed shape lists).  Usage: python tests/gpu_fuzz.py [seed] [n_gemm] [n_attn] [n_ln] [n_gang]  (n_ln also counts the row-mover shapes)"""
+fixed shape lists).  Usage: python tests/gpu_fuzz.py [seed] [n_gemm] [n_attn] [n_ln] [n_gang]  (n_ln also counts the row-mover shapes and the optimizer tables)"""
 import os
 import random
 import sys
@@ -464,6 +464,51 @@ def fuzz_gang(rng, n):
             guard(f'gang #{it}.{j} {what}', guards[j])
 
 
+def fuzz_optimizer(rng, n):
+    """dav_adamw_flat on random segment tables: 1 .. 300 segments of 64 k elements (tiny ones dominate; now and then a last segment
+    that is no multiple of 64), random lr / weight decay per segment, random keep_grad / zero_grad / grad_scale, with and without the
+    bf16 mirror — ONE step per draw against the float64 kcheck.adamw_ref of the same input state, per element."""
+    import math
+    for it in range(n):
+        nseg = rng.choice([1, 2, 3, 17, 64, 150, 300, rng.randint(1, 300)])
+        sizes = [64 * rng.choice([1, 1, 1, 1, 1, 2, 3, 9, 36, rng.randint(1, 600)]) for _ in range(nseg)]
+        if rng.random() < 0.3:
+            sizes[-1] = 64 * rng.randint(0, 3) + 4 * rng.randint(1, 15)
+        ends = [sum(sizes[:i + 1]) for i in range(nseg)]
+        N = ends[-1]
+        hyper = []
+        for _ in range(nseg):
+            hyper += [10.0 ** rng.uniform(-4, -2), rng.choice([0.0, 0.0, 0.05, 0.3])]
+        keep = torch.tensor([rng.random() < 0.5 for _ in range(nseg)], device=dev, dtype=torch.uint8)
+        zero_grad, mirror, use_keep = rng.random() < 0.5, rng.random() < 0.7, rng.random() < 0.7
+        gs, step = rng.choice([1.0, 1.0, 0.37, 0.013]), rng.randint(1, 5)
+        via_dev = rng.random() < 0.3                                  # the same factor as a device scalar
+        seg, hy = torch.tensor(ends, device=dev, dtype=torch.int64), torch.tensor(hyper, device=dev)
+        cnt = torch.tensor(sizes, device=dev)
+        gsc = torch.repeat_interleave(torch.tensor([10.0 ** rng.randint(-4, 1) for _ in range(nseg)], device=dev), cnt)
+        p0, g0, gp = torch.randn(N, device=dev) * 0.02, torch.randn(N, device=dev) * gsc, torch.randn(N, device=dev) * gsc
+        m0, v0 = (0.1 * gp, 0.05 * gp * gp) if step > 1 else (torch.zeros(N, device=dev), torch.zeros(N, device=dev))
+        bc = torch.tensor([1 - 0.9 ** step, math.sqrt(1 - 0.95 ** step)], device=dev)
+        p, g, m, v = p0.clone(), g0.clone(), m0.clone(), v0.clone()
+        pb, ssq = kc.poisoned((N,), BF16, dev), kc.poisoned((1,), F32, dev)
+        sc = torch.tensor([gs], device=dev)
+        ops.adamw_flat(p, g, m, v, pb if mirror else None, seg, hy, nseg, 0.9, 0.95, 1e-8, bc, grad_scale=1.0 if via_dev else gs,
+                       sumsq_out=ssq, zero_grad=zero_grad, keep_grad=keep if use_keep else None, gscale_dev=sc if via_dev else None)
+        tag = f'adamw #{it} n={N} nseg={nseg} step{step} gs={gs}{" dev" if via_dev else ""} zero_grad={int(zero_grad)} keep={int(use_keep)} mirror={int(mirror)}'
+        r = kc.adamw_ref(p0, g0, m0, v0, seg, hy, 0.9, 0.95, 1e-8, bc, float(sc))
+        for k, got in (('p', p), ('m', m), ('v', v)):
+            elem(f'{tag} {k}', 'fuzz_optimizer ' + k, got, r[k], r['b' + k])
+        if mirror:
+            same(tag + ' mirror', pb, p.to(BF16))
+        km = torch.repeat_interleave(keep, cnt).bool() if use_keep else torch.zeros(N, device=dev, dtype=torch.bool)
+        if not zero_grad:
+            km[:] = True
+        same(tag + ' gradients kept', g[km], g0[km])
+        same(tag + ' gradients zero-filled', g[~km], torch.zeros(int((~km).sum()), device=dev))
+        want = float(g0.double().pow(2).sum())
+        elem(tag + ' sumsq', 'fuzz_optimizer sumsq', ssq[0], torch.tensor(want, dtype=torch.float64, device=dev), kc.adamw_sumsq_bound(N, want))
+
+
 if __name__ == '__main__':
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     ng, na, nl, ngg = (int(sys.argv[i]) if len(sys.argv) > i else d for i, d in ((2, 150), (3, 60), (4, 60), (5, 60)))
@@ -476,6 +521,7 @@ if __name__ == '__main__':
     fuzz_ln_fused(rng, nl)
     fuzz_gang(rng, ngg)
     fuzz_rows(rng, nl)
+    fuzz_optimizer(rng, nl)
     print(f'fuzz seed {seed}: {len(FAILS)} failures')
     for f in FAILS[:20]:
         print('  ', f)

@@ -1292,6 +1292,49 @@ def _pairs(B, nv, na, Wd, tag, seed):
         guard(nm + ' a', ga)
 
 
+def drnd(n, seed, scale=1.0):
+    """n fp32 normals drawn ON the device (the long buffers of the grid-cap cases)"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    return torch.randn(n, device=dev, generator=g) * scale
+
+
+def _drop_path_rows(Bq, rq, Dq, seed):
+    """dav_rows_axpy (per element against float64: the multiply-add may be contracted, so it is not bit-exact; out of place and in
+    place over y) and dav_rows_scale_cast (one product, one rounding: bit-exact, guarded) with zeros among the per-sample scales"""
+    tag = f'B{Bq} rows{rq} D{Dq}'
+    R = Bq * rq
+    res, yb = rnd(R, Dq, seed=seed), rnd(R, Dq, seed=seed + 1)
+    sc = torch.tensor([0.0 if b % 3 == 0 else 1.25 for b in range(Bq)], device=dev)
+    srow = sc.repeat_interleave(rq)[:, None]
+    res0, y0, sc0 = res.clone(), yb.clone(), sc.clone()
+    ref = res.double() + srow.double() * yb.double()
+    bound = kc.rows_axpy_bound(res, yb, srow, ref)
+    g = kc.Guarded(R, Dq, F32, device=dev)
+    ops.rows_axpy(res, yb, sc, Bq, rq, Dq, g.t)
+    report(f'rows_axpy {tag}', rel(g.t, res + yb * srow), 1e-6)
+    elem(f'rows_axpy {tag}', 'rows_axpy', g.t, ref, bound)
+    guard(f'rows_axpy {tag}', g)
+    kept(f'rows_axpy {tag} res, y, scale', torch.cat([res.flatten(), yb.flatten(), sc]), torch.cat([res0.flatten(), y0.flatten(), sc0]))
+    gy = kc.Guarded(R, Dq, F32, device=dev, fill=yb)
+    ops.rows_axpy(res, gy.t, sc, Bq, rq, Dq, gy.t)                   # in place over y
+    report(f'rows_axpy in place {tag}', rel(gy.t, res + yb * srow), 1e-6)
+    elem(f'rows_axpy in place {tag}', 'rows_axpy', gy.t, ref, bound)
+    guard(f'rows_axpy in place {tag}', gy)
+    kept(f'rows_axpy in place {tag} res', res, res0)
+    # backward: the rows of a dropped sample are 0 x g.  IEEE 754 gives a product the xor of its factors' signs, so a negative g
+    # there yields -0 in the kernel AND in torch's (g * s).to(bf16): the reference is torch's own result, compared bit for bit
+    # (kc.exact counts a -0 against a +0 as a difference: tests/test_kcheck.py), not a +0 fill.  The -0 feeds a GEMM: harmless.
+    gq = rnd(R, Dq, seed=seed + 2)
+    gq[:rq] = -gq[:rq].abs()                                        # sample 0 is dropped (scale 0): all negative
+    want = (gq * srow).to(BF16)
+    go = kc.Guarded(R, Dq, BF16, device=dev)
+    ops.rows_scale_cast(gq, sc, Bq, rq, Dq, go.t)
+    report(f'rows_scale_cast exact {tag}', float((go.t != want).sum()), 0.0)
+    same(f'rows_scale_cast {tag}', go.t, want)
+    report(f'rows_scale_cast {tag} dropped rows are zeros', float(go.t[:rq].float().abs().max()), 0.0)
+    guard(f'rows_scale_cast {tag}', go)
+
+
 @check
 def misc_kernels():
     # row movers, loss and pairs: a toy shape, then the bench workload's
@@ -1305,28 +1348,36 @@ def misc_kernels():
         _patch_loss(S['B'], C, H, W, f'C{C} B{S["B"]} {H}x{W}', seed=146, edges=True)
     for Wd in S['widths']:
         _pairs(S['B'], S['nv'], S['na'], Wd, f'B{S["B"]} {S["nv"]}x{S["na"]}x{Wd}', seed=148)
-    # DropPath row kernels
-    Bq, rq, Dq = 5, 7, 192
-    res, yb, sc = rnd(Bq * rq, Dq, seed=61), rnd(Bq * rq, Dq, seed=62), torch.tensor([0., 1.25, 1.25, 0., 1.25], device=dev)
-    outp = kc.poisoned(res.shape, F32, dev)
-    ops.rows_axpy(res, yb, sc, Bq, rq, Dq, outp)
-    refp = res + yb * sc.repeat_interleave(rq)[:, None]
-    report('rows_axpy', rel(outp, refp), 1e-6)
-    ops.rows_axpy(res, yb, sc, Bq, rq, Dq, yb)                      # in place over y
-    report('rows_axpy in place', rel(yb, refp), 1e-6)
-    gq = rnd(Bq * rq, Dq, seed=63)
-    ob = kc.poisoned((Bq * rq, Dq), BF16, dev)
-    ops.rows_scale_cast(gq, sc, Bq, rq, Dq, ob)
-    report('rows_scale_cast exact', float((ob != (gq * sc.repeat_interleave(rq)[:, None]).to(BF16)).sum()), 0.0)
-    # casts / norm / adamw
+    # DropPath row kernels: the toy shape, one float4 per row, four trips of the column loop with a ragged last one (D = 772),
+    # and more rows than the grid has waves (9000 > 8192: the row-stride loop)
+    for i, (Bq, rq, Dq) in enumerate([(5, 7, 192), (3, 2, 4), (2, 3, 772), (9, 1000, 8)]):
+        _drop_path_rows(Bq, rq, Dq, seed=61 + 10 * i)
+    # casts: n < 4 (the tail kernel alone), a ragged tail behind the float4 part, and one trip more than the grid cap of
+    # 8192 x 256 float4 covers; every output guarded, bit-exact round-to-nearest-even
     x = rnd(1000, 77, seed=51)
     y = kc.poisoned((1000, 77), BF16, dev)
     ops.cast_bf16(x, y)
     report('cast_bf16 exact', float((y != x.to(BF16)).sum()), 0.0)
+    for n in (1, 2, 3, 5, 77003, 8192 * 1024 + 1027):
+        xs = drnd(n, seed=300 + n % 97)
+        before = xs.clone()
+        g = kc.Guarded(1, n, BF16, device=dev)
+        ops.cast_bf16(xs, g.t)
+        same(f'cast_bf16 n={n}', g.t.view(-1), xs.to(BF16))
+        guard(f'cast_bf16 n={n}', g)
+        kept(f'cast_bf16 n={n} input', xs, before)
     for shape in [(64, 16, 768), (3, 5, 128), (1, 4)]:
         a, b = rnd(*shape, seed=91), rnd(*shape, seed=92)
         o32, ob = ops.add_cast(a, b)
         report(f'add_cast {shape}', float((o32 != a + b).sum()) + float((ob != (a + b).to(BF16)).sum()), 0.0)
+    for n in (4, 8192 * 1024 + 1028):                              # (ops.add_cast allocates its outputs: the C ABI directly, into guards)
+        a, b = drnd(n, seed=93), drnd(n, seed=94)
+        g32, gb = kc.Guarded(1, n, F32, device=dev), kc.Guarded(1, n, BF16, device=dev)
+        ops._lib.check(ops._lib.load().dav_add_cast(a.data_ptr(), b.data_ptr(), g32.ptr(), gb.ptr(), n, ops._stream()), 'dav_add_cast')
+        same(f'add_cast n={n} fp32', g32.t.view(-1), a + b)
+        same(f'add_cast n={n} bf16', gb.t.view(-1), (a + b).to(BF16))
+        guard(f'add_cast n={n} fp32', g32)
+        guard(f'add_cast n={n} bf16', gb)
     yt = kc.poisoned((77, 1000), BF16, dev)
     ops.cast_transpose_bf16(x, yt)
     report('cast_transpose exact', float((yt != x.t().to(BF16)).sum()), 0.0)
@@ -1342,6 +1393,26 @@ def misc_kernels():
         n_bad = int((yi.view(torch.int16) != xi.t().contiguous().to(BF16).view(torch.int16)).sum())
         report(f'cast_transpose_grouped {tuple(xi.shape)} bit-exact', float(n_bad), 0.0)
         guard(f'cast_transpose_grouped {tuple(xi.shape)}', g)
+    # ... and 100 items in one call (the library splits the list into launches of 96): ragged tiles, a single row, three columns
+    pairs, gs = [], []
+    for i in range(100):
+        R, Cc = [(64, 64), (65, 3), (1, 130), (70, 129)][i % 4]
+        xi = rnd(R, Cc, seed=400 + i)
+        g = kc.Guarded(Cc, R, BF16, device=dev)
+        pairs.append((xi, g.t))
+        gs.append(g)
+    ops.cast_transpose_grouped(pairs)
+    bad = stray = 0
+    for (xi, yi), g in zip(pairs, gs):
+        bad += kc.exact(yi.reshape(-1), xi.t().to(BF16).reshape(-1))[0]      # (flat: a [130, 1] transpose keeps the strides of its source)
+        stray += g.stray()[0]
+    report('cast_transpose_grouped 100 items bit-exact', float(bad), 0.0)
+    report('cast_transpose_grouped 100 items guards', float(stray), 0.0)
+
+
+def _optimizer_one_shape():
+    """the checks this family had before it was held per element (one size, two segments with equal hyper-parameters, whole-tensor
+    norms against torch.optim.AdamW over three steps) — kept as they were"""
     flat = rnd(1234567, seed=52)
     out, ws = kc.poisoned((1,), F32, dev), torch.empty(1024, device=dev)
     ops.l2norm(flat, out, ws, 0.5)
@@ -1400,6 +1471,280 @@ def misc_kernels():
     report('adamw skipped step: gradients zero-filled, sumsq reported', float(gz.abs().max()) + abs(float(ssq) / float(g0.double().pow(2).sum()) - 1.0), 1e-5)
 
 
+B1, B2, EPS = 0.9, 0.95, 1e-8
+OPT_SLICE = 1 << 22               # elements per float64 reference slice of the long buffers
+
+
+def _bias_corr(step):
+    return torch.tensor([1 - B1 ** step, math.sqrt(1 - B2 ** step)], device=dev)
+
+
+def _table(sizes, decayed, n=None):
+    """kcheck.seg_table on the device; n: the buffer's length where the last segment is cut short of its 64-element padding"""
+    ends, hyper, real = kc.seg_table(sizes, decayed)
+    if n is not None:
+        assert (ends[-2] if len(ends) > 1 else 0) < n <= ends[-1] and n % 4 == 0
+        ends[-1], real = n, real[:n]
+    pad = (~real).nonzero().flatten().to(dev)
+    return dict(ends=ends, n=ends[-1], nseg=len(ends), seg=torch.tensor(ends, device=dev, dtype=torch.int64),
+                hyper=torch.tensor(hyper, device=dev), pad=pad, sizes=[e - s for s, e in zip([0] + ends[:-1], ends)])
+
+
+def _per_seg(T, vals):
+    """per-element copy of a per-segment list (repeat_interleave over the segment lengths)"""
+    return torch.repeat_interleave(torch.as_tensor(vals, device=dev), torch.tensor(T['sizes'], device=dev))
+
+
+def _flat_randn(T, seed, scale=1.0, seg_scale=None):
+    """n normals drawn on the device, scaled per segment, exactly +0 on the padding"""
+    x = drnd(T['n'], seed, scale)
+    if seg_scale is not None:
+        x *= _per_seg(T, seg_scale)
+    x[T['pad']] = 0.0
+    return x
+
+
+def product_table():
+    """A segment table of the kind util/flat.py builds for the product, from parameter sizes alone: two layers of a D = 192 block
+    (norm, qkv, proj, norm, fc1, fc2 with their biases), three 1 x D tokens, a size that is no multiple of 64, a parameter that makes
+    its end a multiple of 4096, one of 1024 behind it (an end on a multiple of 1024 that is none of 4096) and then 40 parameters of
+    64 elements: the second 1024-element sweep of that workgroup crosses 16 of them.  wd = 0 on the 1-D sizes."""
+    D = 192
+    layer = [D, D, 3 * D * D, 3 * D, D * D, D, D, D, 4 * D * D, 4 * D, 4 * D * D, D]
+    dec = [s > 4 * D for s in layer]
+    sizes, decayed = list(layer), list(dec)
+    c = sum(sizes)                                                  # (all multiples of 64 so far)
+    sizes += [(-c) % 4096 or 4096, 1024] + [64] * 40 + [D, D, D, 1000]
+    decayed += [True, False] + [False] * 40 + [False, False, False, True]
+    sizes += layer
+    decayed += dec
+    T = _table(sizes, decayed)
+    e = T['ends']
+    assert e[12] % 4096 == 0 and e[13] % 4096 == 1024 and all(e[13 + i] == e[13] + 64 * i for i in range(41))
+    hy = T['hyper'].view(-1, 2).tolist()
+    assert all(hy[i] != hy[i + 1] for i in range(len(hy) - 1))     # neighbours differ in lr or wd
+    keep = [0] * T['nseg']
+    keep[2], keep[-1] = 1, 1                                        # a 2-D weight and the last parameter
+    for i in range(14, 54):
+        keep[i] = i & 1                                             # alternating inside the run of 64-element segments
+    T['keep'] = torch.tensor(keep, device=dev, dtype=torch.uint8)
+    T['gscale'] = [10.0 ** ((i * 5) % 7 - 4) for i in range(T['nseg'])]      # gradient magnitude per parameter: 1e-4 .. 1e2
+    return T
+
+
+def adamw_call(tag, T, st, g, step, grad_scale=1.0, gscale_dev=None, mirror=True, zero_grad=False, keep=None, fam='adamw'):
+    """ONE dav_adamw_flat call from the state ``st`` (p, m, v, pb: not modified — the kernel works on copies) with the gradient
+    ``g``, judged against ONE kcheck.adamw_ref step from that same state: p, m, v per element, the mirror bit-exact against the
+    rounding of the p the kernel stored, the padding exactly +0, the gradient untouched / zero-filled / kept, sum(g^2) within its
+    depth bound, and every input the kernel only reads bit-identical afterwards.  Returns the new state (with 'g': the gradient
+    buffer after the call)."""
+    n, seg, hyper = T['n'], T['seg'], T['hyper']
+    p, m, v, gin = st['p'].clone(), st['m'].clone(), st['v'].clone(), g.clone()
+    pb = st['pb'].clone()
+    bc = _bias_corr(step)
+    ssq = kc.poisoned((1,), F32, dev)                              # zeroed by the kernel first (header)
+    ro = [t for t in (seg, hyper, bc, keep, gscale_dev) if t is not None]
+    ro0 = [t.clone() for t in ro]
+    ops.adamw_flat(p, gin, m, v, pb if mirror else None, seg, hyper, T['nseg'], B1, B2, EPS, bc, grad_scale=grad_scale, sumsq_out=ssq,
+                   zero_grad=zero_grad, keep_grad=keep, gscale_dev=gscale_dev)
+    gs = kc.f32(grad_scale) * (float(gscale_dev) if gscale_dev is not None else 1.0)       # the kernel's fp32 product (exact here)
+
+    def ref(lo, hi):
+        return kc.adamw_ref(st['p'][lo:hi], g[lo:hi], st['m'][lo:hi], st['v'][lo:hi], seg, hyper, B1, B2, EPS, bc, gs, start=lo)
+    worst, first = dict(p=0.0, m=0.0, v=0.0), dict(p='', m='', v='')
+    for lo in range(0, n, OPT_SLICE):                               # (the long buffers: float64 temporaries of one slice at a time)
+        hi = min(n, lo + OPT_SLICE)
+        r = ref(lo, hi)
+        for k, got in (('p', p), ('m', m), ('v', v)):
+            ok, ratio, msg = kc.within(got[lo:hi], r[k], r['b' + k], f'{tag} {k} (flat index = {lo} +)')
+            worst[k] = max(worst[k], ratio)                         # (inf for a non-finite element)
+            first[k] = first[k] or msg
+    for k in 'pmv':
+        kc.note(f'{fam} {k}', worst[k])
+        RESULTS.append((f'{tag} {k} elementwise', worst[k], 1.0, worst[k] <= 1.0))
+        print(f'{"PASS" if worst[k] <= 1.0 else "FAIL"} {tag} {k} elementwise: worst err/bound={worst[k]:.3e}' + (f' — {first[k]}' if first[k] else ''), flush=True)
+    if mirror:
+        same(f'{tag} bf16 mirror == bf16(p stored)', pb, p.to(BF16))
+    else:
+        kept(f'{tag} no mirror given: the earlier mirror', pb, st['pb'])
+    pad = T['pad']
+    if pad.numel():
+        same(f'{tag} padding of p, m, v stays +0', torch.cat([p[pad], m[pad], v[pad]]), torch.zeros(3 * pad.numel(), device=dev))
+        if mirror:
+            same(f'{tag} padding of the mirror stays +0', pb[pad], torch.zeros(pad.numel(), device=dev, dtype=BF16))
+    if zero_grad:
+        km = _per_seg(T, keep if keep is not None else torch.zeros(T['nseg'], device=dev, dtype=torch.uint8)).bool()
+        same(f'{tag} zero_grad: gradients outside keep_grad are +0', gin[~km], torch.zeros(int((~km).sum()), device=dev))
+        kept(f'{tag} zero_grad: gradients inside keep_grad', gin, g, km)
+    else:
+        kept(f'{tag} gradients (zero_grad off)', gin, g)
+    want = float(g.double().pow(2).sum())
+    elem(f'{tag} fused sumsq', f'{fam} sumsq', ssq[0], torch.tensor(want, dtype=torch.float64, device=dev), kc.adamw_sumsq_bound(n, want))
+    for i, (t, t0) in enumerate(zip(ro, ro0)):
+        kept(f'{tag} read-only input {i}', t, t0)
+    return dict(p=p, m=m, v=v, pb=pb if mirror else st['pb'], g=gin)
+
+
+def _fresh_state(T, seed, trained=False):
+    """|p| ~ 0.02, the padding +0; m = v = 0 (step 1) or the moments of an earlier gradient; the mirror starts poisoned"""
+    p = _flat_randn(T, seed, 0.02)
+    if trained:
+        g0 = _flat_randn(T, seed + 1, 1.0, T.get('gscale'))
+        m, v = 0.1 * g0, 0.05 * g0 * g0
+    else:
+        m, v = torch.zeros(T['n'], device=dev), torch.zeros(T['n'], device=dev)
+    return dict(p=p, m=m, v=v, pb=kc.poisoned((T['n'],), BF16, dev))
+
+
+def _adamw_product_table():
+    T = product_table()
+    print(f'product-like table: {T["n"]} elements, {T["nseg"]} segments', flush=True)
+    st = _fresh_state(T, 500)
+    # three consecutive calls: bias corrections of steps 1 .. 3, the gradient changes sign and scale in between
+    for step, scale, zg in ((1, 1.0, False), (2, -3e-3, True), (3, 40.0, True)):
+        g = _flat_randn(T, 510 + step, scale, T['gscale'])
+        if step == 1:
+            g[::7] = 0.0                                            # zeros among the gradients (and m = v = 0: 0 / eps)
+        st = adamw_call(f'adamw product table step{step}', T, st, g, step, zero_grad=zg, keep=T['keep'])
+    base = dict(p=st['p'], m=st['m'], v=st['v'], pb=st['pb'])
+    g = _flat_randn(T, 520, 0.5, T['gscale'])
+    host = adamw_call('adamw product table grad_scale 0.37', T, base, g, 4, grad_scale=0.37)
+    sc = torch.tensor([0.37], device=dev)
+    devs = adamw_call('adamw product table gscale_dev 0.37', T, base, g, 4, gscale_dev=sc)
+    same('adamw gscale_dev == grad_scale (bit-equal p, m, v, mirror)', torch.cat([devs[k].float() for k in ('p', 'm', 'v', 'pb')]),
+         torch.cat([host[k].float() for k in ('p', 'm', 'v', 'pb')]))
+    nomir = adamw_call('adamw product table without mirror', T, base, g, 4, grad_scale=0.37, mirror=False)
+    same('adamw without mirror == with mirror (bit-equal p, m, v)', torch.cat([nomir[k] for k in 'pmv']), torch.cat([host[k] for k in 'pmv']))
+    # the skipped step (gscale_dev = 0: a non-finite loss or norm): parameters, moments and mirror untouched, gradients still
+    # zero-filled outside keep_grad, sum(g^2) still reported
+    sc.zero_()
+    pz, mz, vz, pbz, gz, ssq = base['p'].clone(), base['m'].clone(), base['v'].clone(), base['pb'].clone(), g.clone(), kc.poisoned((1,), F32, dev)
+    ops.adamw_flat(pz, gz, mz, vz, pbz, T['seg'], T['hyper'], T['nseg'], B1, B2, EPS, _bias_corr(4), sumsq_out=ssq, zero_grad=True,
+                   keep_grad=T['keep'], gscale_dev=sc)
+    report('adamw skipped step: p, m, v, mirror untouched',
+           float((pz != base['p']).sum() + (mz != base['m']).sum() + (vz != base['v']).sum() + (pbz != base['pb']).sum()), 0.0)
+    kept('adamw skipped step: p, m, v', torch.cat([pz, mz, vz]), torch.cat([base[k] for k in 'pmv']))
+    kept('adamw skipped step: mirror', pbz, base['pb'])
+    km = _per_seg(T, T['keep']).bool()
+    want = float(g.double().pow(2).sum())
+    report('adamw skipped step: gradients zero-filled, sumsq reported', float(gz[~km].abs().max()) + abs(float(ssq) / want - 1.0), 1e-5)
+    same('adamw skipped step: gradients outside keep_grad are +0', gz[~km], torch.zeros(int((~km).sum()), device=dev))
+    kept('adamw skipped step: gradients inside keep_grad', gz, g, km)
+    elem('adamw skipped step: fused sumsq', 'adamw sumsq', ssq[0], torch.tensor(want, dtype=torch.float64, device=dev), kc.adamw_sumsq_bound(T['n'], want))
+
+
+def _adamw_degenerate_and_contract():
+    for tag, sizes, dec, n in (('one segment of 4', [4], [True], 4),
+                               ('4096 + 4: a second workgroup with one float4', [64, 4036], [False, True], 4100),
+                               ('last segment of 64', [1000, 8192, 64], [True, True, False], None)):
+        T = _table(sizes, dec, n)
+        keep = torch.tensor([i & 1 for i in range(T['nseg'])], device=dev, dtype=torch.uint8)
+        adamw_call(f'adamw {tag}', T, _fresh_state(T, 530, trained=True), _flat_randn(T, 531), 2, grad_scale=0.37, zero_grad=True, keep=keep)
+    T = _table([64, 64], [True, False])
+    st, g, bc = _fresh_state(T, 540), _flat_randn(T, 541), _bias_corr(1)
+    wide = torch.zeros(T['n'] + 4, device=dev)
+    snap = torch.cat([st['p'], st['m'], st['v'], g])
+
+    def call(p, gg, m, v, nseg):
+        ops.adamw_flat(p, gg, m, v, None, T['seg'], T['hyper'], nseg, B1, B2, EPS, bc)
+    rejected('adamw n % 4 != 0', lambda: call(st['p'][:126], g[:126], st['m'][:126], st['v'][:126], 2))
+    rejected('adamw p offset by one element (misaligned)', lambda: call(wide[1:1 + T['n']], g, st['m'], st['v'], 2))
+    rejected('adamw nseg = 0', lambda: call(st['p'], g, st['m'], st['v'], 0))
+    kept('adamw rejected calls: state', torch.cat([st['p'], st['m'], st['v'], g]), snap)
+
+
+def _adamw_grid_cap():
+    """n = 16384 x 4096 + 2 x 4096 + 1732: one element more than the capped grid covers in one trip would do; this size class has
+    a ragged second trip of three workgroups, each searching its segment again.  About 300 segments; the 64-element ones sit at
+    the head, and around and behind element 16384 x 4096 — the part only the second trip reaches.  One step, data drawn on the
+    device, float64 reference in slices."""
+    import random
+    t0 = _now()
+    n = kc.ADAMW_GRID_CAP * kc.ADAMW_CHUNK + 2 * 4096 + 1732
+    rng = random.Random(5)
+    head = [rng.choice([64] * 5 + [192, 576, 768, 2304, 36864, 147456, 589824]) for _ in range(240)]
+    tail = [64] * 40 + [1000] + [64] * 8 + [192] * 4 + [2304] + [64] * 10 + [1152, 1988]
+    pad = lambda s: -(-s // 64) * 64                                # noqa: E731
+    t_start = kc.ADAMW_GRID_CAP * kc.ADAMW_CHUNK - 1024             # the run of 64s straddles the end of the first trip
+    fill = t_start - sum(head)
+    assert fill > 0 and fill % 64 == 0
+    mid = [fill // 3 // 64 * 64, fill // 3 // 64 * 64]
+    mid.append(fill - sum(mid))
+    sizes = head + mid + tail
+    T = _table(sizes, [s > 768 for s in sizes], n)
+    assert T['n'] == n and sum(pad(s) for s in sizes[:-1]) + 1988 == n and T['ends'][len(head) + 2] == t_start
+    assert sum(1 for e in T['ends'] if e > kc.ADAMW_GRID_CAP * kc.ADAMW_CHUNK) >= 40 and kc.adamw_grid(n) == (kc.ADAMW_GRID_CAP, 2)
+    T['keep'] = torch.tensor([(i % 3 == 0) for i in range(T['nseg'])], device=dev, dtype=torch.uint8)
+    T['gscale'] = [10.0 ** ((i * 5) % 7 - 4) for i in range(T['nseg'])]
+    print(f'grid-cap table: {n} elements, {T["nseg"]} segments', flush=True)
+    st = _fresh_state(T, 550, trained=True)
+    g = _flat_randn(T, 552, 1.0, T['gscale'])
+    adamw_call('adamw grid cap', T, st, g, 3, grad_scale=0.37, zero_grad=True, keep=T['keep'], fam='adamw grid cap')
+    torch.cuda.synchronize()
+    print(f'wall time of the grid-cap case: {_now() - t0:.2f} s', flush=True)
+
+
+def _l2norm_sizes():
+    for n in (1, 3, 4, 1023, 262144 + 1, 1234567):
+        # magnitudes over six decades; the float4 part's first and last element and every tail element carry a visible share
+        x = drnd(n, 560 + n % 89) * 10.0 ** (torch.arange(n, device=dev) % 7 - 3).float()
+        big = float(x.double().norm()) + 1.0
+        for i in {0, max(0, (n >> 2 << 2) - 1), *range(n >> 2 << 2, n)}:
+            x[i] = 0.1 * big * (-1) ** i
+        x0 = x.clone()
+        out, ws = kc.poisoned((1,), F32, dev), torch.full((1024,), float('nan'), device=dev)
+        ops.l2norm(x, out, ws, 0.5)
+        want = kc.f32(0.5) * float(x.double().norm())
+        report(f'l2norm n={n}', abs(float(out) - want) / want, 1e-6)
+        elem(f'l2norm n={n}', 'l2norm', out[0], torch.tensor(want, dtype=torch.float64, device=dev), kc.l2norm_bound(n, want))
+        kept(f'l2norm n={n} input', x, x0)
+    for n in (3, 1027, 262144 + 3):                                 # zero everywhere but ONE element, in the tail workgroup 0 reads
+        x = torch.zeros(n, device=dev)
+        x[n - 1] = -3.25
+        out, ws = kc.poisoned((1,), F32, dev), torch.full((1024,), float('nan'), device=dev)
+        ops.l2norm(x, out, ws, 2.0)
+        elem(f'l2norm n={n} one tail element', 'l2norm', out[0], torch.tensor(6.5, dtype=torch.float64, device=dev), kc.l2norm_bound(n, 6.5))
+    x, out = drnd(64, 570), kc.poisoned((1,), F32, dev)
+    rejected('l2norm n = 0', lambda: ops.l2norm(x[:0], out, torch.empty(1024, device=dev), 1.0))
+    rejected('l2norm workspace of 1023 floats', lambda: ops.l2norm(x, out, torch.empty(1023, device=dev), 1.0))
+    report('l2norm rejected calls leave out poisoned', 0.0 if bool(out.isnan().all()) else 1.0, 0.0)
+
+
+def _step_guard_more():
+    """beyond the cases of _optimizer_one_shape: clip = 0 with a norm given, grad_scale entering the clipped norm, a norm exactly at
+    the limit.  s = min(1, clip / (norm grad_scale + 1e-6)): a product, a sum and a division in fp32 — 4 u of the float64 value."""
+    gn, sc = torch.tensor([316.22775], device=dev), kc.poisoned((1,), F32, dev)
+    one = torch.tensor([2.5], device=dev)
+    ops.step_guard(one, one, gn, 0.0, 1.0, sc, None)
+    report('step_guard clip = 0 with a norm given -> 1', abs(float(sc) - 1.0), 0.0)
+    for tag, clip, gs in (('grad_scale 0.37 in the clipped norm', 50.0, 0.37), ('grad_scale 1/128: below the limit', 3.0, 1.0 / 128),
+                          ('norm exactly at the limit', float(gn), 1.0), ('norm at the limit through grad_scale', 0.25 * float(gn), 0.25)):
+        sc.fill_(float('nan'))
+        ops.step_guard(one, None, gn, clip, gs, sc, None)
+        want = min(1.0, kc.f32(clip) / (float(gn) * kc.f32(gs) + kc.f32(1e-6)))
+        elem(f'step_guard {tag}', 'step_guard', sc[0], torch.tensor(want, dtype=torch.float64, device=dev), 4 * kc.U32 * want)
+        report(f'step_guard {tag}: never above 1', max(0.0, float(sc) - 1.0), 0.0)
+
+
+def _now():
+    import time
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+@check
+def optimizer():
+    """The optimizer pass over the flat buffers: dav_adamw_flat, dav_l2norm, dav_step_guard"""
+    t0 = _now()
+    _optimizer_one_shape()
+    _l2norm_sizes()
+    _step_guard_more()
+    _adamw_product_table()
+    _adamw_degenerate_and_contract()
+    _adamw_grid_cap()
+    print(f'wall time of optimizer(): {_now() - t0:.2f} s', flush=True)
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ''
     print('device:', torch.cuda.get_device_name(0), flush=True)
@@ -1407,7 +1752,7 @@ def main():
         if ':' in kv:
             from deepavfusion_amd import _lib
             _lib.check(_lib.load().dav_tune(int(kv.split(':')[0]), int(kv.split(':')[1])), 'dav_tune')
-    for fn in (gemm_nt, gemm_tn, gemm_tn_gang, attention, dropout, window_attention, layernorm, ln_fused, masking, misc_kernels, patch_gather3d):
+    for fn in (gemm_nt, gemm_tn, gemm_tn_gang, attention, dropout, window_attention, layernorm, ln_fused, masking, misc_kernels, optimizer, patch_gather3d):
         if flt in fn.__name__:
             fn()
     bad = [r for r in RESULTS if not r[3]]

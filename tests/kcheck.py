@@ -354,3 +354,115 @@ def ln_bounds(x, gamma, beta, eps, dy=None):
                bdgamma=U32 * (rows * (d2 * x2).abs().sum(0) + C_LN * (d2.abs() * (1 + x2.abs()) * stat.reshape(-1, 1)).sum(0)),
                bdbeta=U32 * rows * d2.abs().sum(0))
     return out
+
+
+# ---- flat-buffer optimizer pass (dav_adamw_flat, dav_l2norm) and the DropPath row kernels -----------------------------------------
+# Worst err / bound seen on an MI355X (tests/gpu_selfcheck.py optimizer / misc_kernels; the constants below come from the counts
+# in the docstrings, none was fitted to these figures):
+#   adamw_ref p 0.35, m 0.49, v 0.39 (0.9 M elements, 70 segments) and p 0.36, m 0.48, v 0.54 (67 M elements, 309 segments, two trips)
+#   adamw_sumsq_bound 0.03 .. 0.045 (219 workgroups; the atomic adds land in a different order every run) and 0.0012 (16384 workgroups)
+#   l2norm_bound 0.097   rows_axpy_bound 0.48   step_guard (4 u) 0.12
+
+ADAMW_CHUNK = 4096                # elements one workgroup of dav_adamw_flat handles per trip: 256 lanes x 4 float4 of 4
+ADAMW_GRID_CAP = 16384            # its grid is capped here; longer buffers take further trips of the grid-stride loop
+L2NORM_GRID_CAP = 1024            # dav_l2norm: partial sums of at most this many workgroups of 256 lanes, one float4 per lane and trip
+
+
+def f32(x):
+    """the value a C ``float`` argument takes: x rounded to fp32, as a Python float (so float64 arithmetic widens it exactly)"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def seg_table(sizes, decayed, base_lr=1e-2, wd=0.05, align=64):
+    """The flat layout util/flat.py gives a list of parameters: each of ``sizes`` rounded up to ``align`` elements, laid out back to
+    back, one segment per parameter.  Segment i gets lr = base_lr * 0.75^(i mod 7) (a layer-wise scale: neighbours always differ)
+    and weight decay ``wd`` where ``decayed[i]`` else 0 (the 1-D parameters).  Returns (seg_end list, hyper list [lr0, wd0, lr1, ..],
+    real bool mask over the n elements as a CPU tensor: False on the padding behind a size that is no multiple of ``align``)."""
+    ends, hyper, off = [], [], 0
+    for i, (sz, dec) in enumerate(zip(sizes, decayed)):
+        assert sz > 0
+        off += (sz + align - 1) // align * align
+        ends.append(off)
+        hyper += [base_lr * 0.75 ** (i % 7), wd if dec else 0.0]
+    real = torch.zeros(off, dtype=torch.bool)
+    start = 0
+    for sz, e in zip(sizes, ends):
+        real[start:start + sz] = True
+        start = e
+    return ends, hyper, real
+
+
+def seg_expand(seg_end, per_seg, n, start=0):
+    """per-element value of a per-segment table for the elements start .. start + n - 1: element i belongs to the first segment
+    whose seg_end is > i (searchsorted; NOT the kernel's own binary search + walk)"""
+    i = torch.arange(start, start + n, device=seg_end.device, dtype=torch.int64)
+    s = torch.searchsorted(seg_end.to(torch.int64).contiguous(), i, right=True).clamp_max(seg_end.numel() - 1)
+    return per_seg[s]
+
+
+def adamw_ref(p, g, m, v, seg_end, hyper, beta1, beta2, eps, bias_corr, grad_scale, start=0):
+    """ONE float64 AdamW step of dav_adamw_flat from the fp32 state given (``start``: index of p[0] in the flat buffer, for a slice
+    of a long one).  Every scalar the kernel receives as a float enters as its fp32 value widened to float64.
+      g' = g grad_scale;  m' = beta1 m + (1 - beta1) g';  v' = beta2 v + (1 - beta2) g'^2
+      p' = p (1 - lr wd) - (lr / bc1) m' / (sqrt(v') / bc2 + eps)          (bias_corr = [bc1, bc2]: 1 - beta1^t, sqrt(1 - beta2^t))
+    Bounds, counting the kernel's fp32 roundings (u = 2^-24; 1 - beta is exact in fp32 for beta >= 1/2):
+      m' : t1 = beta1 m is rounded once, t2 = (1 - beta1) g' twice (g', the product), the sum once more — at most 2 u |t1| + 3 u |t2|,
+           taken as 4 u (|t1| + |t2|)
+      v' : g' once (it enters squared: 2 u), two products, beta2 v once, the sum once; every term is >= 0, so the errors are
+           relative to v' itself: 6 u v'
+      p' : decay = fl(1 - fl(lr wd)) is off by at most 2 u, p decay is rounded once and so is the difference: u (4 |p| + |p'|);
+           U = step m' / den with step = lr / bc1 and den = sqrt(v') / bc2 + eps carries the error of m' (step bound(m') / den), that of
+           v' through the square root (3 u), and one rounding each of the sqrt, the division by bc2, the addition of eps, step, the
+           product and the last division (6 u): 9 u |U|, taken as 10 u |U|.
+    An fp32 transcription of the kernel's formula against this reference (2^20 elements, 4 steps, gradient scales 1e-6 .. 10,
+    grad_scale 1 / 0.37 / 0.013, zeros in p and g) reached 0.48 of the p bound and 0.64 of the m and v bounds.
+    Returns dict(p, m, v, bp, bm, bv) in float64."""
+    n = p.numel()
+    p64, g64, m64, v64 = (t.detach().double() for t in (p, g, m, v))
+    hy = hyper.detach().float().double().view(-1, 2)
+    lr, wd = seg_expand(seg_end, hy[:, 0], n, start), seg_expand(seg_end, hy[:, 1], n, start)
+    b1, b2, e, gs = f32(beta1), f32(beta2), f32(eps), f32(grad_scale)
+    bc1, bc2 = (float(x) for x in bias_corr.detach().float().double().cpu())
+    gp = g64 * gs
+    t1, t2 = b1 * m64, (1.0 - b1) * gp
+    mn = t1 + t2
+    vn = b2 * v64 + (1.0 - b2) * gp * gp
+    den = vn.sqrt() / bc2 + e
+    step = lr / bc1
+    U = step * mn / den
+    pn = p64 * (1.0 - lr * wd) - U
+    bm = 4 * U32 * (t1.abs() + t2.abs())
+    bv = 6 * U32 * vn
+    bp = U32 * (4 * p64.abs() + pn.abs()) + step * bm / den + 10 * U32 * U.abs()
+    return dict(p=pn, m=mn, v=vn, bp=bp, bm=bm, bv=bv)
+
+
+def adamw_grid(n):
+    """(workgroups, trips of the grid-stride loop) of dav_adamw_flat at n elements"""
+    grid = min(-(-n // ADAMW_CHUNK), ADAMW_GRID_CAP)
+    return grid, -(-n // (grid * ADAMW_CHUNK))
+
+
+def adamw_sumsq_bound(n, sumsq):
+    """dav_adamw_flat's fused sum(g^2), an fp32 sum whose depth is the kernel's: a lane adds 4 squares per float4 and visits 4
+    float4 per trip, then 6 shuffle levels, 4 wave partials, and one atomic add per workgroup into one fp32 word:
+    (16 trips + 6 + 4 + workgroups) u sum(g^2)   (every term >= 0; the rounding of each square rides on its term's count)"""
+    grid, trips = adamw_grid(n)
+    return (16 * trips + 6 + 4 + grid) * U32 * float(sumsq)
+
+
+def l2norm_bound(n, ref):
+    """dav_l2norm: out = scale sqrt(sum x^2).  A lane of the partial kernel adds 4 squares per float4 over its trips (+ 1 tail element
+    in workgroup 0), then 6 shuffle levels and 4 wave partials in fp32: d = 4 trips + 1 + 6 + 4 roundings relative to sum x^2 (all
+    terms >= 0).  The partials are combined in double, so the last stage adds only the square root (which halves the relative
+    error: d / 2), the scale in double and the one rounding of the stored float: (d / 2 + 2) u |ref|."""
+    n4 = n >> 2
+    grid = max(1, min(-(-n4 // 256), L2NORM_GRID_CAP))
+    trips = -(-n4 // (grid * 256))
+    return ((4 * trips + 1 + 6 + 4) / 2 + 2) * U32 * abs(float(ref))
+
+
+def rows_axpy_bound(res, y, s_rows, ref):
+    """out = res + s y per row (dav_rows_axpy): the product and the sum are one rounding each, or one in all where the compiler
+    contracts them to an fma — never bit-exact against either, so: u (|res| + 2 |s y| + |out|).  s_rows: [rows, 1] scale per row."""
+    return U32 * (res.detach().double().abs() + 2 * (s_rows.detach().double() * y.detach().double()).abs() + ref.detach().double().abs())

@@ -313,3 +313,149 @@ def test_f32_attention_bound_is_tight():
     bad = (r['O'] + 3 * r['bO']).float()
     assert K.within(bad, r['O'], K.attn_bounds(q, k, v, None, None, scale, bias=bias)['bO'])[0]
     assert not K.within(bad, r['O'], r['bO'])[0]
+
+
+# ---- the optimizer pass (kcheck.adamw_ref): an fp32 transcription of dav_adamw_flat's formula passes, six ways it could go wrong
+# do not
+
+_ADAMW_SIZES = [192, 36864, 576, 1000] + [64] * 6 + [2304, 192, 192, 768, 40]      # 1000 and 40: padded to 1024 and 64
+_ADAMW_DECAYED = [sz in (36864, 2304, 768) for sz in _ADAMW_SIZES]
+_B1, _B2, _EPS, _GS = 0.9, 0.95, 1e-8, 0.37
+
+
+def _adamw_case():
+    """A flat state of the kind util/flat.py lays out (|p| ~ 0.02, lr wd >= 1e-5 on the decayed segments, padding all zero), in the
+    middle of training (m, v non-zero), and one gradient"""
+    ends, hyper, real = K.seg_table(_ADAMW_SIZES, _ADAMW_DECAYED)
+    n = ends[-1]
+    assert n % 4096 and n > 4096 * 10                              # the last 4096-chunk is a partial one
+    g = _gen(40)
+    p, g0, g1 = (torch.where(real, torch.randn(n, generator=g) * s, torch.zeros(())) for s in (0.02, 1.0, 1.0))     # padding: +0
+    sc = 10.0 ** torch.randint(-4, 1, (len(ends),), generator=g).float()       # gradient magnitude per parameter
+    seg = torch.tensor(ends)
+    g0, g1 = g0 * K.seg_expand(seg, sc, n), g1 * K.seg_expand(seg, sc, n)
+    m, v = 0.1 * g0, 0.05 * g0 * g0
+    bc = torch.tensor([1 - _B1 ** 2, (1 - _B2 ** 2) ** 0.5])
+    return dict(p=p, g=g1, m=m, v=v, seg=seg, hyper=torch.tensor(hyper), bc=bc, ends=ends, n=n, real=real)
+
+
+def _adamw_f32(c, lr=None, wd=None, gs_v=_GS):
+    """dav_adamw_flat's statement order in fp32 torch ops, one rounding per operation (every scalar an fp32 tensor).  lr / wd:
+    per-element tables (default: the case's own); gs_v: the gradient scale used for v (a mutant passes 1)."""
+    f = lambda x: torch.tensor(x, dtype=torch.float32)          # noqa: E731
+    hy = c['hyper'].view(-1, 2)
+    lr = K.seg_expand(c['seg'], hy[:, 0], c['n']) if lr is None else lr
+    wd = K.seg_expand(c['seg'], hy[:, 1], c['n']) if wd is None else wd
+    b1, b2, eps, bc1, bc2 = f(_B1), f(_B2), f(_EPS), c['bc'][0], c['bc'][1]
+    gx, gv = c['g'] * f(_GS), c['g'] * f(gs_v)
+    m = b1 * c['m'] + (1 - b1) * gx
+    v = b2 * c['v'] + (1 - b2) * gv * gv
+    p = c['p'] * (1 - lr * wd) - (lr / bc1) * m / (v.sqrt() / bc2 + eps)
+    assert p.dtype == m.dtype == v.dtype == torch.float32
+    return p, m, v
+
+
+def _adamw_judge(c, p, m, v):
+    """(ok, message) of p, m, v against kcheck.adamw_ref of the case's input state"""
+    r = K.adamw_ref(c['p'], c['g'], c['m'], c['v'], c['seg'], c['hyper'], _B1, _B2, _EPS, c['bc'], _GS)
+    return {k: K.within(got, r[k], r['b' + k], k)[::2] for k, got in (('p', p), ('m', m), ('v', v))}
+
+
+def _nbad(msg):
+    """(number of elements outside the bound, flat index of the worst one) from a ``within`` message"""
+    return int(msg.split(': ')[1].split(' of')[0]), int(msg.split('worst at [')[1].split(']')[0])
+
+
+def test_adamw_fp32_transcription_is_inside_the_bounds():
+    c = _adamw_case()
+    j = _adamw_judge(c, *_adamw_f32(c))
+    assert all(ok for ok, _ in j.values()), j
+    # the padding stays exactly +0 through the formula (what gpu_selfcheck.optimizer asks of the kernel)
+    for t in _adamw_f32(c):
+        assert K.exact(t[~c['real']], torch.zeros(int((~c['real']).sum()))) == (0, '')
+
+
+def test_adamw_first_float4_behind_a_boundary_with_the_neighbours_hyper():
+    """(a) a lane whose segment walk stops one short: 4 elements updated with the previous segment's lr / wd"""
+    c = _adamw_case()
+    hy = c['hyper'].view(-1, 2)
+    lr, wd = K.seg_expand(c['seg'], hy[:, 0], c['n']), K.seg_expand(c['seg'], hy[:, 1], c['n'])
+    e = c['ends'][5]                                               # between two of the 64-element segments
+    lr[e:e + 4], wd[e:e + 4] = lr[e - 1], wd[e - 1]
+    j = _adamw_judge(c, *_adamw_f32(c, lr, wd))
+    assert not j['p'][0] and _nbad(j['p'][1])[0] == 4 and e <= _nbad(j['p'][1])[1] < e + 4, j['p']
+    assert j['m'][0] and j['v'][0]                                 # the moments do not depend on the table
+
+
+def test_adamw_weight_decay_on_a_segment_without():
+    """(b) wd = 0.05 applied to a 1-D parameter"""
+    c = _adamw_case()
+    hy = c['hyper'].view(-1, 2)
+    wd = K.seg_expand(c['seg'], hy[:, 1], c['n'])
+    lo, hi = c['ends'][1], c['ends'][2]                            # the 576-element segment: wd 0
+    assert float(wd[lo:hi].max()) == 0.0
+    wd[lo:hi] = 0.05
+    j = _adamw_judge(c, *_adamw_f32(c, wd=wd))
+    assert not j['p'][0] and _nbad(j['p'][1])[0] > 0.9 * (hi - lo) and lo <= _nbad(j['p'][1])[1] < hi, j['p']
+    assert j['m'][0] and j['v'][0]
+
+
+def test_adamw_one_float4_of_the_last_partial_chunk_not_updated():
+    """(c) a float4 group in the ragged last 4096-chunk keeps its old p / m / v"""
+    c = _adamw_case()
+    p, m, v = _adamw_f32(c)
+    i = c['n'] // 4096 * 4096 + 1028
+    assert i + 4 <= c['n'] and bool(c['real'][i:i + 4].all())
+    for new, old in ((p, c['p']), (m, c['m']), (v, c['v'])):
+        new[i:i + 4] = old[i:i + 4]
+    j = _adamw_judge(c, p, m, v)
+    for k in 'pmv':
+        assert not j[k][0] and _nbad(j[k][1])[0] == 4 and i <= _nbad(j[k][1])[1] < i + 4, j[k]
+
+
+def test_adamw_mirror_taken_from_the_old_parameters():
+    """(d) the bf16 mirror must be ONE rounding of the p just stored: bit-exact, where the old rel <= 4e-3 passes the stale one"""
+    c = _adamw_case()
+    p = _adamw_f32(c)[0]
+    assert K.exact(p.to(BF16), p.to(BF16)) == (0, '')
+    stale = c['p'].to(BF16)
+    assert gpu_selfcheck.rel(stale[:c['ends'][0]], p[:c['ends'][0]]) > 0          # (not the same numbers)
+    n, msg = K.exact(stale, p.to(BF16), 'mirror')
+    assert n > 0.5 * int(c['real'].sum()) and 'mirror' in msg
+
+
+def test_adamw_a_kept_gradient_segment_zero_filled():
+    """(e) zero_grad with keep_grad = 1 on a segment: its gradient must come back bit-identical"""
+    c = _adamw_case()
+    lo, hi = c['ends'][6], c['ends'][7]
+    keep = torch.zeros(c['n'], dtype=torch.bool)
+    keep[lo:hi] = True
+    right = torch.where(keep, c['g'], torch.zeros(()))
+    assert K.changed(right, c['g'], keep) == (0, -1) and K.exact(right[~keep], torch.zeros(c['n'] - (hi - lo))) == (0, '')
+    wrong = torch.zeros(c['n'])
+    n, i = K.changed(wrong, c['g'], keep)
+    assert n == hi - lo and i == lo
+
+
+def test_adamw_second_moment_from_the_unscaled_gradient():
+    """(f) v updated with g instead of g * grad_scale"""
+    c = _adamw_case()
+    j = _adamw_judge(c, *_adamw_f32(c, gs_v=1.0))
+    assert j['m'][0] and not j['v'][0] and not j['p'][0], j
+    assert _nbad(j['v'][1])[0] > 0.9 * int(c['real'].sum())
+
+
+def test_exact_sees_a_negative_zero():
+    """the DropPath backward's dropped rows are checked with ``exact``: -0 where +0 is due is a difference"""
+    z = torch.zeros(4, dtype=BF16)
+    assert K.exact(-z, z)[0] == 4 and K.exact(z, z) == (0, '')
+
+
+def test_depth_bounds_are_not_vacuous():
+    """sum_bound with n = the element count allows a relative 6e-2 at 10^6 elements; the depth bounds stay near 1e-6 (l2norm) and
+    track the workgroup count (the fused sum(g^2): one atomic add each)"""
+    assert K.adamw_grid(4) == (1, 1) and K.adamw_grid(4100) == (2, 1) and K.adamw_grid(16384 * 4096) == (16384, 1)
+    assert K.adamw_grid(16384 * 4096 + 4) == (16384, 2)
+    assert K.adamw_sumsq_bound(900000, 1.0) == (16 + 10 + 220) * K.U32
+    assert K.l2norm_bound(1234567, 2.0) == ((8 + 11) / 2 + 2) * K.U32 * 2.0
+    assert K.l2norm_bound(3, 1.0) == (11 / 2 + 2) * K.U32                          # tail only: no float4 trip
