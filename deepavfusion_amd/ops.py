@@ -748,3 +748,39 @@ def frame_transform(frames, params, size, mean, std, out=None):
     _lib.check(_lib.load().dav_frame_transform_u8(_ptr(frames), B, H, W, _ptr(params), size, m[0], m[1], m[2], s[0], s[1], s[2],
                                                   _ptr(out), _stream()), 'dav_frame_transform_u8')
     return out
+
+
+RESAMPLE_MAX_RATIO = 1024   # dav_resample_max_ratio of include/dav_kernels.h: the reduced rates o, n of dav_wave_resample
+
+
+def wave_resample_tile(o, n, width):
+    """Frames (of ``o`` input samples) one workgroup of dav_wave_resample owns at this geometry: where its tiles meet."""
+    t = _lib.load().dav_wave_resample_tile(int(o), int(n), int(width))
+    _lib.check(min(t, 0), 'dav_wave_resample_tile')
+    return t
+
+
+def wave_resample(wave, taps_kn, o, n, width, out_len=None, gain=None, clamp=False, out=None):
+    """Windowed-sinc polyphase resampling of a batch of waveforms with Pad's mirror, a per-row gain and the clamp to [-1, 1] in
+    the epilogue, one launch (dav_wave_resample).  wave fp32 or int16 [B, L] on the device, unit stride along L (rows may be
+    strided); taps_kn fp32 [2 width + o, n] dense, the table k-major; gain fp32 [B] or None -> fp32 [B, out_len]
+    (default out_len: R = ceil(n L / o)); ``out``: an fp32 [B, out_len] view with unit stride along its rows."""
+    if wave.dtype not in (F32, torch.int16) or wave.dim() != 2 or wave.stride(1) != 1:
+        raise ValueError('wave_resample needs fp32 or int16 waveforms [B, L] with unit stride along L')
+    B, L = wave.shape
+    o, n, width = int(o), int(n), int(width)
+    if taps_kn.dtype != F32 or tuple(taps_kn.shape) != (2 * width + o, n) or not taps_kn.is_contiguous():
+        raise ValueError(f'wave_resample needs a dense fp32 tap table [{2 * width + o}, {n}] (k-major)')
+    if taps_kn.device != wave.device or (gain is not None and gain.device != wave.device):
+        raise ValueError('waveforms, taps and gains live on different devices')
+    if gain is not None and (gain.dtype != F32 or tuple(gain.shape) != (B,) or not gain.is_contiguous()):
+        raise ValueError(f'wave_resample needs dense fp32 gains [{B}]')
+    out_len = -(-n * L // o) if out_len is None else int(out_len)
+    if out is None:
+        out = torch.empty(B, out_len, dtype=F32, device=wave.device)
+    elif out.dtype != F32 or tuple(out.shape) != (B, out_len) or out.stride(1) != 1:
+        raise ValueError(f'wave_resample writes fp32 [{B}, {out_len}] with unit stride along its rows')
+    _lib.check(_lib.load().dav_wave_resample(_ptr(wave), int(wave.dtype == torch.int16), B, L, wave.stride(0) if B > 1 else L,
+                                             _ptr(taps_kn), o, n, width, _ptr(gain), int(bool(clamp)), _ptr(out), out_len,
+                                             out.stride(0) if B > 1 else out_len, _stream()), 'dav_wave_resample')
+    return out

@@ -6,7 +6,9 @@ data-loader workers.  Same class names and constructor arguments:
 
 works on a batch of waveforms [B, S] (or [B, 1, S] / [1, S]) resident on the device and yields [B, 1, n_mels, frames];
 ``LogMelSpectrogram`` is the fused form (one kernel, incl. the ``[:, :, :-1]`` of datasets.py:242).
-Pad / RandomVol are index / scale plumbing (torch); the STFT, mel projection and log run in csrc/mel.hip."""
+Pad / RandomVol are index / scale plumbing (torch); the STFT, mel projection and log run in csrc/mel.hip.
+``Resample`` is the sinc resampler the reference's loader applies to every track (datasets.py:176-181), in csrc/data/resample.hip;
+``PrepareWaveform`` is Resample -> Pad -> RandomVol in that kernel's one launch (data.audio_resample=gpu)."""
 import math
 import random
 
@@ -58,6 +60,122 @@ class Pad(torch.nn.Module):
         while waveform.shape[-1] < self.samples:
             waveform = torch.cat((waveform, torch.flip(waveform, dims=(-1,))), dim=-1)
         return waveform[..., :self.samples]
+
+
+def resample_geometry(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """(o, n, width, taps per phase) of torchaudio's sinc resampler: the rates reduced by their gcd, the filter's half width in
+    input samples, and K = 2 width + o."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq < 1 or new_freq < 1 or lowpass_filter_width < 1:
+        raise ValueError('rates and the filter width must be positive')
+    g = math.gcd(orig_freq, new_freq)
+    o, n = orig_freq // g, new_freq // g
+    width = int(math.ceil(lowpass_filter_width * o / (min(o, n) * rolloff)))
+    return o, n, width, 2 * width + o
+
+
+def resample_taps(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The fp32 tap table [n, K] of torchaudio.functional.resample (resampling_method='sinc_interp_hann', its default),
+    restated from its published source and evaluated in float64: phase p, tap k weighs sinc(t) cos^2(pi t / (2 lpw)) base / o
+    at t = clamp((k - width) / o - p / n, +-lpw / base) * base with base = min(o, n) rolloff."""
+    o, n, width, K = resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    base = min(o, n) * rolloff
+    idx = (np.arange(K, dtype=np.float64) - width) / o
+    t = (-np.arange(n, dtype=np.float64)[:, None] / n + idx[None, :]) * base
+    t = np.clip(t, -lowpass_filter_width, lowpass_filter_width)
+    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    safe = np.where(t == 0, 1.0, t)
+    sinc = np.where(t == 0, 1.0, np.sin(safe) / safe)
+    return (sinc * window * (base / o)).astype(np.float32)
+
+
+def resample_tile(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """Frames (of o input samples, n output samples) one workgroup of the resampling kernel owns for this pair of rates: outputs
+    j and j + 1 with (j + 1) % (n * tile) == 0 come from different workgroups (asked of the library, not restated)."""
+    from ..ops import wave_resample_tile
+    o, n, width, _ = resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    return wave_resample_tile(o, n, width)
+
+
+class Resample(torch.nn.Module):
+    """torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults (windowed sinc, Hann, lowpass_filter_width 6,
+    rolloff 0.99) — what the reference's loader applies to every track (datasets.py:176-181) — on dav_wave_resample: waveforms
+    [B, S] (or [B, 1, S] / [1, S]; fp32 or int16, which is scaled by 2^-15) on the device -> fp32 with ceil(n S / o) samples per
+    row.  Equal rates return the input object, no launch.  The table is computed in float64 (numpy) and held in fp32."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann'):
+        super().__init__()
+        if resampling_method not in ('sinc_interp_hann', 'sinc_interpolation'):
+            raise NotImplementedError(f'resampling_method={resampling_method}: only the Hann-windowed sinc (torchaudio\'s default) '
+                                      'is on the MI355X path')
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.lowpass_filter_width, self.rolloff = lowpass_filter_width, rolloff
+        self.o, self.n, self.width, self.ntaps = resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        if self.orig_freq != self.new_freq:
+            from ..ops import RESAMPLE_MAX_RATIO
+            if max(self.o, self.n) > RESAMPLE_MAX_RATIO:
+                raise ValueError(f'{orig_freq} -> {new_freq} Hz reduces to {self.o} : {self.n}; the kernel takes ratios up to '
+                                 f'{RESAMPLE_MAX_RATIO}')
+            taps = torch.from_numpy(resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff))
+            self.register_buffer('taps', taps, persistent=False)                              # [n, K], torchaudio's layout
+            self.register_buffer('taps_kn', taps.t().contiguous(), persistent=False)          # [K, n], the kernel's
+
+    def out_samples(self, samples):
+        return -(-self.n * int(samples) // self.o)
+
+    def _rows(self, waveform):
+        if not waveform.is_cuda:
+            raise RuntimeError('the resampler runs on an MI355X (cuda) device; there is no CPU fallback')
+        if waveform.dtype not in (torch.float32, torch.int16):
+            waveform = waveform.to(torch.float32)
+        x = waveform.reshape(-1, waveform.shape[-1]) if waveform.dim() != 2 else waveform
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        if self.orig_freq != self.new_freq and self.taps_kn.device != x.device:
+            self.to(x.device)
+        return x
+
+    def _launch(self, x, out_len, gain, clamp):
+        from ..ops import wave_resample
+        return wave_resample(x, self.taps_kn, self.o, self.n, self.width, out_len=out_len, gain=gain, clamp=clamp)
+
+    def forward(self, waveform):
+        if self.orig_freq == self.new_freq:
+            return waveform
+        x = self._rows(waveform)
+        y = self._launch(x, self.out_samples(x.shape[-1]), None, False)
+        return y.view(*waveform.shape[:-1], y.shape[-1])
+
+
+class PrepareWaveform(Resample):
+    """Compose([Resample(orig_freq, new_freq), Pad(dur, new_freq), RandomVol(gain, per_sample=True)]) in ONE launch: the mirror
+    padding, the gain and the clamp are the resampling kernel's epilogue.  The gains are drawn and converted exactly as RandomVol
+    does (random.uniform once per row in row order, torch.pow(10, g / 20) on an fp32 device tensor), so under the same
+    random.seed the two forms agree bit for bit.  ``gain=None``: no gain and no clamp (the probe's eval transform).  With equal
+    rates nothing is launched: Pad and RandomVol run as they are.  -> fp32 [B, int(dur * new_freq)] (leading dims kept)."""
+
+    def __init__(self, orig_freq, new_freq, dur, gain=(-6, 6), lowpass_filter_width=6, rolloff=0.99):
+        super().__init__(orig_freq, new_freq, lowpass_filter_width=lowpass_filter_width, rolloff=rolloff)
+        self.samples = int(dur * self.new_freq)
+        self.gain = gain
+        self._pad = Pad(dur, self.new_freq)
+        self._vol = RandomVol(gain, per_sample=True) if gain is not None else None
+
+    def forward(self, waveform):
+        if self.orig_freq == self.new_freq:
+            if not waveform.is_cuda:
+                raise RuntimeError('the waveform front-end runs on an MI355X (cuda) device; there is no CPU fallback')
+            x = waveform if waveform.dtype == torch.float32 else waveform.to(torch.float32) * (1.0 / 32768.0 if waveform.dtype == torch.int16 else 1.0)
+            x = self._pad(x)
+            return self._vol(x) if self._vol is not None else x
+        x = self._rows(waveform)
+        g = None
+        if self.gain is not None:
+            db = torch.tensor([random.uniform(self.gain[0], self.gain[1]) for _ in range(x.shape[0])], dtype=torch.float32, device=x.device)
+            g = torch.pow(10.0, db / 20.0)
+        y = self._launch(x, self.samples, g, self.gain is not None)
+        return y.view(*waveform.shape[:-1], self.samples)
 
 
 def _fbank_htk(n_freqs, f_min, f_max, n_mels, sample_rate):

@@ -13,7 +13,8 @@ and ``ClipShards`` serves them as the reference's VideoDataset does: an audio wi
 with ``train=True``, centred otherwise), one stored frame from inside that window, and the annotation.  What it yields is RAW —
 a uint8 frame [H, W, 3] and the waveform in [-1, 1] — because the transforms run on the device
 (util/frame_transforms.py, util/audio_transforms.py).  One frame size, one frame-time grid and one audio rate per shard set;
-there is no resampler."""
+there is no resampler in the loader: a set kept at its tracks' own rate (make_shards.py --keep-rate) is resampled on the device
+(``ClipShards(resample=True)``, data.audio_resample=gpu)."""
 import json
 import os
 
@@ -107,11 +108,16 @@ class ClipShards(torch.utils.data.Dataset):
     A clip no longer than ``audio_dur`` comes back whole from start = 0 (audio_transforms.Pad mirrors it out on the device).
     ``anno`` is {'class': label} for a labelled set, else the index.
 
+    ``resample=True`` accepts a set stored at another rate than ``audio_rate`` (``stored_rate``, from meta.json): the window is cut
+    at the stored rate, as the reference cuts before it resamples — int(audio_dur * stored_rate) samples from
+    round(start * stored_rate) — and comes back as raw int16 (half the bytes to the device) for
+    audio_transforms.PrepareWaveform(stored_rate, audio_rate, audio_dur), which scales, resamples and pads it there.
+
     The draws are a pure function of (seed, epoch, index) — ``set_epoch`` — not of worker scheduling: a run repeats with any number
     of loader workers.  With ``train=False`` the epoch is left out too: the same frame of the same clip at every call.  The arrays
     are memory-mapped lazily, in the process (loader worker) that first reads them."""
 
-    def __init__(self, path, partition='train', audio_dur=3.0, audio_rate=16000, train=True, seed=0):
+    def __init__(self, path, partition='train', audio_dur=3.0, audio_rate=16000, train=True, seed=0, resample=False):
         self.dir = os.path.join(str(path), partition)
         if not os.path.isfile(os.path.join(self.dir, META)):
             raise FileNotFoundError(f'{self.dir}: no {META} (write a shard set with tools/make_shards.py or ClipShardWriter)')
@@ -124,12 +130,16 @@ class ClipShards(torch.utils.data.Dataset):
         self.frame_times = np.asarray(m['frame_times'], np.float64)
         self.audio_rate, self.clip_dur = int(m['audio_rate']), float(m['clip_dur'])
         self.class_names, self.multi_label = m.get('class_names'), bool(m.get('multi_label'))
-        if int(audio_rate) != self.audio_rate:
+        self.stored_rate = self.audio_rate
+        self.resample = bool(resample)
+        if int(audio_rate) != self.stored_rate and not resample:
             raise ValueError(f'{self.dir} holds audio at {self.audio_rate} Hz, {audio_rate} Hz asked for: there is no resampler, '
-                             'set data.audio_rate to the stored rate or rebuild the shards')
-        self.samples = int(round(self.clip_dur * self.audio_rate))
+                             'set data.audio_rate to the stored rate or rebuild the shards (or resample on the device: '
+                             'ClipShards(resample=True), data.audio_resample=gpu)')
+        self.audio_rate = int(audio_rate)                          # the rate asked for; stored_rate is what the files hold
+        self.samples = int(round(self.clip_dur * self.stored_rate))
         self.audio_dur, self.train, self.seed, self.epoch = float(audio_dur), bool(train), int(seed), 0
-        self.window = min(int(self.audio_dur * self.audio_rate), self.samples)
+        self.window = min(int(self.audio_dur * self.stored_rate), self.samples)
         for name, size in ((FRAMES, self.n * self.F * self.hw[0] * self.hw[1] * 3), (AUDIO, self.n * self.samples * 2)):
             have = os.path.getsize(os.path.join(self.dir, name))
             if have != size:
@@ -186,9 +196,12 @@ class ClipShards(torch.utils.data.Dataset):
             raise IndexError(idx)
         self._open()
         start, f = self.sample(idx)
-        s0 = min(int(round(start * self.audio_rate)), self.samples - self.window)
+        s0 = min(int(round(start * self.stored_rate)), self.samples - self.window)
         frame = torch.from_numpy(np.array(self._frames[idx, f]))
-        wave = torch.from_numpy(np.asarray(self._audio[idx, s0:s0 + self.window], np.float32) / 32768.0)
+        if self.resample:                                          # cut at the stored rate, raw: the device scales and resamples
+            wave = torch.from_numpy(np.array(self._audio[idx, s0:s0 + self.window]))
+        else:
+            wave = torch.from_numpy(np.asarray(self._audio[idx, s0:s0 + self.window], np.float32) / 32768.0)
         if self._labels is None:
             return frame, wave, idx
         lab = self._labels[idx]

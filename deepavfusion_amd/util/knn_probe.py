@@ -16,7 +16,8 @@ Documented differences from the reference:
     follow ``env.workers`` (the reference forces at least one);
   - ``dataset=synthetic`` is a labelled synthetic set (seeded class prototypes + seeded noise); ``dataset=shards`` reads a labelled
     clip-shard partition (util/clip_shards.py: pre-decoded clips, ``train=False``) and runs the reference's eval transforms on the
-    device (EvalFrameTransform; Pad -> LogMelSpectrogram, no RandomVol).  VGGSound / AudioSet by name need PyAV and torchaudio,
+    device (EvalFrameTransform; Pad -> LogMelSpectrogram, no RandomVol; with ``audio_resample=gpu`` a set stored at its tracks' own
+    rate goes through PrepareWaveform(gain=None): Resample -> Pad in one launch).  VGGSound / AudioSet by name need PyAV and torchaudio,
     which are not dependencies of this project.  Python callers may pass any dataset that yields
     ``(image, spec, {'class': label})`` — the reference's contract; multi-hot labels ([num_classes] per clip) select the AP / AUC
     metrics.
@@ -188,8 +189,9 @@ class EvalAVNNProbe:
             from .frame_transforms import EvalFrameTransform
             if not probe_args.get('data_path'):
                 raise ValueError('nn_probe.dataset=shards needs nn_probe.data_path (default: data.data_path)')
+            resample = probe_args.get('audio_resample', 'off') == 'gpu'      # a set stored at its tracks' own rate: resampled on the device
             self.db = ClipShards(probe_args.data_path, probe_args.get('partition') or 'test', audio_dur=float(probe_args.audio_dur),
-                                 audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed)
+                                 audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed, resample=resample)
             if not self.db.has_labels:
                 raise ValueError(f'{self.db.dir} has no labels.npy: the nearest-neighbour probe needs a labelled shard set')
             self.multi_label = self.db.multi_label
@@ -197,12 +199,18 @@ class EvalAVNNProbe:
                 raise ValueError('nn_probe.bank_samples belongs to the synthetic set; shards take nn_probe.bank_partition')
             if bank_partition:
                 self.bank_db = ClipShards(probe_args.data_path, bank_partition, audio_dur=float(probe_args.audio_dur),
-                                          audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed)
+                                          audio_rate=int(probe_args.audio_rate), train=False, seed=self.seed, resample=resample)
                 if not self.bank_db.has_labels or self.bank_db.multi_label != self.multi_label:
                     raise ValueError(f'{self.bank_db.dir}: the bank needs labels of the same kind as {self.db.dir}')
+                if self.bank_db.stored_rate != self.db.stored_rate:
+                    raise ValueError(f'{self.bank_db.dir} holds audio at {self.bank_db.stored_rate} Hz, {self.db.dir} at '
+                                     f'{self.db.stored_rate} Hz: the bank and the evaluation set share one front-end')
             self.frame_frontend = EvalFrameTransform(int(probe_args.image_size))
-            self.audio_frontend = aT.Compose([aT.Pad(float(probe_args.audio_dur), int(probe_args.audio_rate)),
-                                              aT.LogMelSpectrogram(int(probe_args.audio_rate), int(probe_args.audio_mels))])
+            if resample:                 # Resample -> Pad in one launch, no RandomVol (gain=None); int16 windows in
+                pad = aT.PrepareWaveform(self.db.stored_rate, int(probe_args.audio_rate), float(probe_args.audio_dur), gain=None)
+            else:
+                pad = aT.Pad(float(probe_args.audio_dur), int(probe_args.audio_rate))
+            self.audio_frontend = aT.Compose([pad, aT.LogMelSpectrogram(int(probe_args.audio_rate), int(probe_args.audio_mels))])
         elif self.dataset in ('vggsound', 'audioset'):
             raise NotImplementedError(f'nn_probe.dataset={self.dataset}: synthetic and shards are on the MI355X path '
                                       '(the reference datasets need PyAV/torchaudio; decode them with tools/make_shards.py)')
@@ -256,7 +264,9 @@ class EvalAVNNProbe:
         E.set_ln_fuse('off')
         try:
             for image, spec, anno in loader:
-                spec = spec.to(self.device, non_blocking=True).float()
+                spec = spec.to(self.device, non_blocking=True)
+                if spec.dtype != torch.int16:                     # int16: raw windows of audio_resample=gpu, scaled by the kernel
+                    spec = spec.float()
                 image = image.to(self.device, non_blocking=True)
                 image = self.frame_frontend(image) if self.frame_frontend is not None else image.float()
                 if self.audio_frontend is not None:

@@ -393,6 +393,24 @@ int dav_log10_eps(const float* x, float eps, long n, float* y, hipStream_t strea
 int dav_frame_transform_u8(const uint8_t* frames, int B, int H, int W, const int* params, int S, float mean0, float mean1,
                            float mean2, float std0, float std1, float std2, float* out, hipStream_t stream);
 
+/* ---- audio resampling of the input stage (csrc/data/resample.hip) ----------------------------- */
+/* The reference's loader resamples every track from its own rate (datasets.py:176-181, torchaudio's default windowed-sinc
+ * polyphase Resample), then Pad -> RandomVol (util/audio_transforms.py:8-27); here the three are ONE launch over a batch.
+ * With o = orig / gcd, n = new / gcd, K = 2 width + o taps per phase and the waveform x zero-padded by `width` in front:
+ *   r[f n + p] = sum_k taps[p][k] xpad[f o + k], cut to R = ceil(n L / o) samples   (fp32, one k-ordered fmaf chain per sample)
+ *   out[b][j] = c(gain[b] r_b[m(j)]),  m(j) = j' < R ? j' : 2 R - 1 - j',  j' = j mod 2 R   (Pad's mirror; a plain cut for
+ *   out_len <= R);  c clamps to [-1, 1] when `clamp` is set; gain NULL = 1.
+ * wave: fp32, or int16 (wave_is_i16; scaled by 2^-15, exact), [B][L] with a row stride of in_rs elements.  taps_kn: the fp32
+ * table K-MAJOR, [K][n] (lanes read consecutive phases).  out fp32 [B][out_len], row stride out_rs elements.
+ * o, n <= dav_resample_max_ratio and K <= 14336 (56 KB of staged samples), B <= 65535, L, out_len <= 2^30, in_rs >= L,
+ * out_rs >= out_len (else -1); wave aligned to its element, taps_kn, gain and out to 4 bytes (else -5; no wider access is
+ * made, so the strides carry no alignment of their own).  dav_wave_resample_tile: the number of frames (of o input samples) one
+ * workgroup owns at this geometry — the seam of the tiling, for tests — or -1 for a refused geometry. */
+enum { dav_resample_max_ratio = 1024 };   /* the cap on o and n */
+int dav_wave_resample_tile(int o, int n, int width);
+int dav_wave_resample(const void* wave, int wave_is_i16, int B, int L, long in_rs, const float* taps_kn, int o, int n, int width,
+                      const float* gain, int clamp, float* out, int out_len, long out_rs, hipStream_t stream);
+
 /* ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------- */
 /* out[b, :] = v / max(||v||_2, 1e-12) with v = mean over l of x[b, l, :]: the x.mean(dim=1) + F.normalize(p=2, dim=1) of
  * util/knn_probe.py:102-110.  x fp32 [B, L, D] with row stride ld_row (>= D) and batch stride ld_batch (elements); out dense

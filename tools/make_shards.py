@@ -10,7 +10,9 @@
 Every frame is resized on its short side and centre-cropped on its long side to the one H x W of the set (PIL, bilinear); a clip
 with fewer frames than --frames, a track at another rate (there is no resampler) or shorter than --clip-dur is refused by name.
 --frames frames are taken evenly from those present, frame k at time (k + 0.5) clip_dur / frames.  More than one class on a line
-makes the set multi-label.  PIL and wave are needed by this tool only."""
+makes the set multi-label.  --keep-rate stores the tracks at their OWN rate instead of --audio-rate (44.1 or 48 kHz as decoded; all
+tracks of a set must share it, one at another rate is refused by name) and records it in meta.json: train.py resamples such a set
+on the device (data.audio_resample=gpu), with the filter the reference's loader applies.  PIL and wave are needed by this tool only."""
 import argparse
 import os
 import sys
@@ -45,6 +47,12 @@ def load_wav(path, rate, samples):
     return (x.sum(1) // x.shape[1]).astype(np.int16)
 
 
+def wav_rate(path):
+    import wave
+    with wave.open(path, 'rb') as w:
+        return w.getframerate()
+
+
 def read_labels(path):
     out = {}
     with open(path) as f:
@@ -66,6 +74,8 @@ def main():
     ap.add_argument('--frames', type=int, default=8)
     ap.add_argument('--clip-dur', type=float, default=10.0)
     ap.add_argument('--audio-rate', type=int, default=16000)
+    ap.add_argument('--keep-rate', action='store_true',
+                    help="store the tracks at their own (shared) rate, not --audio-rate; resampled on the device (data.audio_resample=gpu)")
     a = ap.parse_args()
     H, W = a.hw
     clips = sorted(d for d in os.listdir(a.src) if os.path.isdir(os.path.join(a.src, d, 'frames')))
@@ -79,6 +89,8 @@ def main():
             raise SystemExit(f'labels.csv has no class for {missing[:5]}')
         names = sorted({n for c in clips for n in labels[c]})
         multi = any(len(labels[c]) > 1 for c in clips)
+    if a.keep_rate:                                              # the set's rate is the first track's; load_wav refuses any other by name
+        a.audio_rate = wav_rate(os.path.join(a.src, clips[0], 'audio.wav'))
     times = [(k + 0.5) * a.clip_dur / a.frames for k in range(a.frames)]
     samples = int(round(a.clip_dur * a.audio_rate))
     with ClipShardWriter(a.data_path, a.partition, a.frames, (H, W), times, a.audio_rate, a.clip_dur, names, multi) as wr:

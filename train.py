@@ -72,6 +72,14 @@ def load_config(name='deepavfusion', overrides=()):
     return cfg
 
 
+def audio_resample_mode(value):
+    """data.audio_resample / nn_probe.audio_resample: 'off' | 'gpu' (a bare ``off`` on the command line is YAML's False)."""
+    mode = 'off' if value in (None, False, 'off') else value
+    if mode not in ('off', 'gpu'):
+        raise ValueError(f'audio_resample={value}: off or gpu')
+    return mode
+
+
 class SyntheticAV(torch.utils.data.Dataset):
     """ImageNet-normalised frames ~ N(0,1); log10-mel spectrograms in about [-7, 4] (train.py:50-54, datasets.py:242) — or,
     with ``wave_samples`` set (data.audio_frontend=gpu), raw waveforms in [-1, 1] that the device-side front-end
@@ -119,6 +127,9 @@ def main_worker(local_rank, args):
                                   'datasets need PyAV/torchaudio; decode them into clip shards with tools/make_shards.py)')
     shards = args.data.dataset == 'shards'
     gpu_frontend = args.data.get('audio_frontend', 'auto') == 'gpu' or shards     # waveforms in, log-mel computed on the device
+    resample = audio_resample_mode(args.data.get('audio_resample', 'off')) == 'gpu'
+    if resample and not shards:
+        raise ValueError('data.audio_resample=gpu resamples a clip-shard set stored at its tracks\' own rate: it needs data.dataset=shards')
     if shards:
         from deepavfusion_amd.util.clip_shards import ClipShards
         if args.data.get('audio_frontend', 'auto') == 'loader':
@@ -127,7 +138,7 @@ def main_worker(local_rank, args):
         if not args.data.get('data_path'):
             raise ValueError('data.dataset=shards needs data.data_path=<folder holding <partition>/meta.json>')
         dataset = ClipShards(args.data.data_path, args.data.get('partition') or 'train', audio_dur=args.data.audio_dur,
-                             audio_rate=args.data.audio_rate, train=True, seed=args.env.seed or 0)
+                             audio_rate=args.data.audio_rate, train=True, seed=args.env.seed or 0, resample=resample)
         if len(dataset) < eff_batch_size:
             raise ValueError(f'{dataset.dir}: {len(dataset)} clips are fewer than one global batch of {eff_batch_size}')
     else:
@@ -180,7 +191,10 @@ def main_worker(local_rank, args):
         from deepavfusion_amd.util import audio_transforms as aT
         from deepavfusion_amd.util.frame_transforms import TrainFrameTransform
         frame_frontend = TrainFrameTransform(args.data.image_size, scale=(args.data.crop_min, 1.))
-        frontend = aT.Compose([aT.Pad(args.data.audio_dur, args.data.audio_rate), aT.RandomVol(per_sample=True), frontend])
+        if resample:                                                 # datasets.py:176-181 + Pad + RandomVol as one launch; int16 in
+            frontend = aT.Compose([aT.PrepareWaveform(dataset.stored_rate, args.data.audio_rate, args.data.audio_dur), frontend])
+        else:
+            frontend = aT.Compose([aT.Pad(args.data.audio_dur, args.data.audio_rate), aT.RandomVol(per_sample=True), frontend])
     print(f'Start training for {args.opt.epochs} epochs')
     for epoch in range(start_epoch, args.opt.epochs):
         if num_tasks > 1:
@@ -207,7 +221,9 @@ def train_one_epoch(loader, trainer, epoch, device, args, graphed=None, frontend
             lr = lr_sched.adjust_learning_rate(trainer.optimizer, epoch + step / len(loader), args)
         image = image.to(device, non_blocking=True)
         image = frame_frontend(image) if frame_frontend is not None else image.float()     # uint8 [B, H, W, 3] -> [B, 3, size, size]
-        audio = audio.to(device, non_blocking=True).float()
+        audio = audio.to(device, non_blocking=True)
+        if audio.dtype != torch.int16:                               # int16: raw windows of data.audio_resample=gpu, scaled by the kernel
+            audio = audio.float()
         if frontend is not None:
             audio = frontend(audio)                 # [B, samples] -> [B, 1, n_mels, 64 * dur] on the device
         if graphed is not None:
