@@ -98,6 +98,7 @@ SIGNATURES = {
     'dav_knn_topk_f32': [_p] * 6 + [_i, _i, _i, _i, _l, _l, _i, _i, _i, _p, _p, _p, _sz, _p],
     'dav_knn_topk_wide_f32': [_p] * 6 + [_i, _i, _i, _i, _l, _l, _i, _i, _i, _p, _p, _p, _sz, _p],
     'dav_knn_vote_f32': [_p, _p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p],
+    'dav_ap_auc_f64': [_p, _l, _i, _i, _i, _p, _l, _l, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p],
     'dav_frame_transform_u8': [_p, _i, _i, _i, _p, _i, _f, _f, _f, _f, _f, _f, _p, _p],
     'dav_wave_resample_tile': [_i, _i, _i],
     'dav_wave_resample': [_p, _i, _i, _i, _l, _p, _i, _i, _i, _p, _i, _p, _i, _l, _p],

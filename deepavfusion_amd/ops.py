@@ -722,6 +722,87 @@ def knn_vote(top_val, top_idx, labels, num_classes, k, inv_t, self_offset=-1, ou
     return scores, (None if multi else pred.long())
 
 
+# ---- multi-label probe metrics (csrc/probe/ap_auc.hip) -------------------------------------------------------------------
+
+AP_AUC_MAX_ROWS = 32768   # dav_ap_auc_max_rows of include/dav_kernels.h: one workgroup holds a whole column in LDS
+AP_AUC_MAX_VIEWS = 4
+
+
+def ap_auc_workspace_bytes(V, n, C):
+    """C * ((n + 31) / 32) * 4: the truth as one bit mask per class — the formula of dav_ap_auc_f64 (include/dav_kernels.h); the
+    views share it."""
+    return C * ((n + 31) // 32) * 4
+
+
+def ap_auc(y, scores=None, *, nbr=None, nbr_val=None, nbr_labels=None, out=None, workspace=None):
+    """Per-class average precision and ROC AUC of V score views against multi-hot truth, sklearn's definitions with ties grouped
+    (dav_ap_auc_f64).  y uint8 [n, C] with unit column stride.  Exactly one form of scores:
+      dense      ``scores`` fp32 [V, n, C] (or [n, C]) with unit column stride; rows may be wider than C (a view);
+      neighbour  ``nbr`` int32 (or int64: converted) [V, n] (or [n]), ``nbr_val`` fp32 of the same shape, ``nbr_labels`` multi-hot
+                 uint8 [N, C]: the score of (row i, class c) is nbr_labels[nbr[v, i], c] * nbr_val[v, i].
+    -> (ap fp64 [V, C], auc fp64 [V, C] with NaN where a column has one class only, pos int32 [C]); ``out`` = (ap, auc, pos) dense
+    tensors to write into."""
+    if y.dim() != 2 or y.dtype != torch.uint8 or y.stride(1) != 1 or (y.shape[0] > 1 and y.stride(0) < y.shape[1]):
+        raise ValueError('ap_auc needs the truth as uint8 [n, C] with unit column stride and rows that do not overlap')
+    n, C_ = y.shape
+    dense = scores is not None
+    if dense == (nbr is not None or nbr_val is not None or nbr_labels is not None):
+        raise ValueError('ap_auc takes either dense scores or the neighbour form (nbr, nbr_val, nbr_labels), not both or neither')
+    if not 1 <= n <= AP_AUC_MAX_ROWS or C_ < 1:
+        raise ValueError(f'ap_auc: {n} rows x {C_} classes (1 <= rows <= {AP_AUC_MAX_ROWS}, classes >= 1)')
+    dev = y.device
+    if dense:
+        if scores.dim() == 2:
+            scores = scores.unsqueeze(0)
+        if scores.dim() != 3 or scores.dtype != F32 or tuple(scores.shape[1:]) != (n, C_) or scores.stride(2) != 1:
+            raise ValueError(f'ap_auc needs dense-form scores as fp32 [V, {n}, {C_}] with unit column stride')
+        V = scores.shape[0]
+        rs = scores.stride(1) if n > 1 else C_
+        vs = scores.stride(0) if V > 1 else 0
+        if rs < C_ or vs < 0:
+            raise ValueError('ap_auc: the rows of a score view must not overlap')
+        operands = (scores,)
+    else:
+        if nbr is None or nbr_val is None or nbr_labels is None:
+            raise ValueError('ap_auc: the neighbour form needs nbr, nbr_val and nbr_labels')
+        if nbr.dim() == 1:
+            nbr, nbr_val = nbr.unsqueeze(0), nbr_val.unsqueeze(0)
+        if nbr.dim() != 2 or nbr.shape[1] != n or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
+            raise ValueError(f'ap_auc needs nbr as integer indices [V, {n}]')
+        if nbr_val.dtype != F32 or nbr_val.shape != nbr.shape:
+            raise ValueError(f'ap_auc needs nbr_val as fp32 {list(nbr.shape)}')
+        if nbr_labels.dim() != 2 or nbr_labels.dtype != torch.uint8 or nbr_labels.shape[1] != C_ or nbr_labels.shape[0] < 1:
+            raise ValueError(f'ap_auc needs nbr_labels as multi-hot uint8 [N, {C_}]')
+        V = nbr.shape[0]
+        if nbr.dtype != torch.int32 or not nbr.is_contiguous():
+            nbr = nbr.to(torch.int32).contiguous()
+        nbr_val, nbr_labels = nbr_val.contiguous(), nbr_labels.contiguous()
+        rs = vs = 0
+        operands = (nbr, nbr_val, nbr_labels)
+    if not 1 <= V <= AP_AUC_MAX_VIEWS:
+        raise ValueError(f'ap_auc takes 1 to {AP_AUC_MAX_VIEWS} views, not {V}')
+    if any(t.device != dev for t in operands):
+        raise ValueError('the truth and the scores live on different devices')
+    if out is None:
+        out = (torch.empty(V, C_, dtype=torch.float64, device=dev), torch.empty(V, C_, dtype=torch.float64, device=dev),
+               torch.empty(C_, dtype=torch.int32, device=dev))
+    ap, auc, pos = out
+    for t, dt, shape in ((ap, torch.float64, (V, C_)), (auc, torch.float64, (V, C_)), (pos, torch.int32, (C_,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'ap_auc writes dense ap / auc fp64 [{V}, {C_}] and pos int32 [{C_}]')
+    nbytes = ap_auc_workspace_bytes(V, n, C_)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f'ap_auc needs a workspace of {nbytes} bytes')
+    _lib.check(_lib.load().dav_ap_auc_f64(_ptr(y), y.stride(0) if n > 1 else C_, n, C_, V, _ptr(scores) if dense else None, rs, vs,
+                                          None if dense else _ptr(nbr), None if dense else _ptr(nbr_val),
+                                          None if dense else _ptr(nbr_labels), 0 if dense else int(nbr_labels.shape[0]),
+                                          _ptr(ap), _ptr(auc), _ptr(pos), _ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), _stream()), 'dav_ap_auc_f64')
+    return ap, auc, pos
+
+
 # ---- frame transform of the input stage (csrc/data/frames.hip) -----------------------------------------------------------
 
 FRAME_PARAM_COLS = 9    # i, j, h, w, RH, RW, top, left, flip (include/dav_kernels.h)

@@ -28,7 +28,14 @@ synthetic) or, without one, the eval set itself with each query's own row exclud
 their classes with the weight exp(similarity / temperature) (the sum view on the MEAN similarity of its modalities), by
 dav_knn_topk_wide_f32 + dav_knn_vote_f32.  New keys after the reference's: ``{audio,image,fusion,all}_knn{k}_acc``, or
 ``_knn{k}_ap`` / ``_knn{k}_auc`` on the vote scores of multi-hot sets.
+
+``nn_probe.metrics`` (multi-hot sets only; ``host`` by default): where AP / AUC are computed.  ``host``: the predictions and vote
+scores are copied back and ``average_precision`` / ``roc_auc`` below run in numpy, as in the reference; ``device``: dav_ap_auc_f64
+(ops.ap_auc) computes them per class for all four views in one call per protocol and only [4, C] doubles and the positives per
+class come back — the ``seen`` mask, the error for a class every clip has and the mean stay on the host (``device_metrics``), the
+keys and their order are the same.
 """
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -135,23 +142,67 @@ def vote_metrics(scores, preds, labels, multi_label, k):
     return dict(out)
 
 
-def knn_vote_predictions(feats, bank_feats, bank_labels, num_classes, k, temperature, exclude_self):
+METRICS = ('host', 'device')                              # nn_probe.metrics
+
+
+def metrics_mode(value):
+    """nn_probe.metrics -> 'host' (also for a missing key) or 'device'; anything else is refused."""
+    mode = 'host' if value is None else str(value)
+    if mode not in METRICS:
+        raise ValueError(f'nn_probe.metrics={value}: one of {", ".join(METRICS)}')
+    return mode
+
+
+def metrics_on_device(mode, multi_label, n):
+    """Whether the AP / AUC of an evaluation over n clips run in dav_ap_auc_f64: asked for, a multi-hot set (single-label sets have
+    accuracies only), and a column fits the kernel."""
+    return metrics_mode(mode) == 'device' and bool(multi_label) and n <= ops.AP_AUC_MAX_ROWS
+
+
+def device_metrics(ap, auc, pos, tag):
+    """The host half of nn_probe.metrics=device: ap / auc [4, C] in the kernel's view order and pos [C] as ops.ap_auc returns
+    them (numpy) -> {'<mod>_<tag>_ap', '<mod>_<tag>_auc'} over the classes that occur, the keys and their order as probe_metrics
+    (tag 'nn') / vote_metrics (tag 'knn<k>') give them.  A class that occurs in every clip has no AUC: the error of roc_auc."""
+    seen = pos > 0
+    out = OrderedDict()
+    for mod in MODALITIES:
+        a = auc[_VIEW[mod]][seen]
+        if np.isnan(a).any():
+            raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+        out[f'{mod}_{tag}_ap'] = float(ap[_VIEW[mod]][seen].mean())
+        out[f'{mod}_{tag}_auc'] = float(a.mean())
+    return dict(out)
+
+
+def knn_vote_scores(feats, bank_feats, bank_labels, num_classes, k, temperature, exclude_self):
     """feats / bank_feats = (image, audio, fusion) features [n, D] / [N, D]; bank_labels class ids [N] or multi-hot [N, C].
-    -> {modality: (vote scores [n, C], voted class [n] or None)} (device tensors).  ``exclude_self``: the bank IS the query set, row
-    q of it is skipped for query q (one more entry is fetched for it)."""
+    -> (vote scores [4, n, C], voted class [4, n] or None) in the kernel's view order (device tensors).  ``exclude_self``: the bank
+    IS the query set, row q of it is skipped for query q (one more entry is fetched for it)."""
     kk = k + int(bool(exclude_self))
     val, idx = ops.knn_topk(feats, bank_feats, k=kk, sum_view=True)
     M = len(feats)
     inv_t = [1.0 / temperature] * M + [1.0 / (temperature * M)]              # the sum view votes on the mean similarity
     lab = bank_labels.to(torch.uint8) if bank_labels.dim() == 2 else bank_labels
-    scores, pred = ops.knn_vote(val, idx, lab, num_classes, k, inv_t, self_offset=0 if exclude_self else -1)
+    return ops.knn_vote(val, idx, lab, num_classes, k, inv_t, self_offset=0 if exclude_self else -1)
+
+
+def knn_vote_predictions(feats, bank_feats, bank_labels, num_classes, k, temperature, exclude_self):
+    """knn_vote_scores by modality: -> {modality: (vote scores [n, C], voted class [n] or None)} (device tensors)."""
+    scores, pred = knn_vote_scores(feats, bank_feats, bank_labels, num_classes, k, temperature, exclude_self)
     return OrderedDict((mod, (scores[_VIEW[mod]], None if pred is None else pred[_VIEW[mod]])) for mod in MODALITIES)
 
 
-def knn_predictions(v_feats, a_feats, mm_feats, labels, k=2):
-    """util/knn_probe.py:113-131 as ONE kernel call: -> {modality: (labels of the 2nd neighbour, its score)} (device tensors)."""
+def knn_neighbours(v_feats, a_feats, mm_feats, k=2):
+    """util/knn_probe.py:113-128 as ONE kernel call: -> (index [4, n] of every clip's 2nd neighbour, its score [4, n]) in the
+    kernel's view order (device tensors)."""
     val, idx = ops.knn_topk((v_feats, a_feats, mm_feats), (v_feats, a_feats, mm_feats), k=k, sum_view=True)
-    return OrderedDict((mod, (labels[idx[_VIEW[mod], :, 1]], val[_VIEW[mod], :, 1])) for mod in MODALITIES)
+    return idx[:, :, 1], val[:, :, 1]
+
+
+def knn_predictions(v_feats, a_feats, mm_feats, labels, k=2):
+    """util/knn_probe.py:113-131: -> {modality: (labels of the 2nd neighbour, its score)} (device tensors)."""
+    idx, val = knn_neighbours(v_feats, a_feats, mm_feats, k)
+    return OrderedDict((mod, (labels[idx[_VIEW[mod]]], val[_VIEW[mod]])) for mod in MODALITIES)
 
 
 class EvalAVNNProbe:
@@ -165,6 +216,8 @@ class EvalAVNNProbe:
         self.frame_frontend = self.audio_frontend = None       # shards: raw frames / waveforms in, transforms on the device
         self.k = None if probe_args.get('k') is None else int(probe_args.get('k'))            # None: the reference's protocol only
         self.temperature = float(probe_args.get('temperature') or 0.07)
+        self.metrics = metrics_mode(probe_args.get('metrics'))                               # multi-hot sets: where AP / AUC run
+        self._metrics_warned = False
         if self.k is not None and not 1 <= self.k < ops.KNN_MAX_K:
             raise ValueError(f'nn_probe.k={self.k}: the weighted vote takes 1 .. {ops.KNN_MAX_K - 1} neighbours')
         if self.k is not None and not self.temperature > 0:
@@ -283,23 +336,41 @@ class EvalAVNNProbe:
     @torch.no_grad()
     def evaluate(self, model, epoch=0):
         v_feats, a_feats, mm_feats, labels = self.extract(model)
-        preds = knn_predictions(v_feats, a_feats, mm_feats, labels)
         multi_label = self.multi_label if self.multi_label is not None else labels.dim() == 2
-        out = probe_metrics(OrderedDict((m, (p.cpu().numpy(), s.cpu().numpy())) for m, (p, s) in preds.items()),
-                            labels.cpu().numpy(), multi_label)
+        truth = None                                           # metrics=device: the multi-hot labels as uint8, made once
+        if metrics_on_device(self.metrics, multi_label, labels.shape[0]):
+            # the reference's ypred * yscore[:, None] is formed inside the kernel from the neighbour's row of the labels
+            truth = labels.to(torch.uint8)
+            idx, val = knn_neighbours(v_feats, a_feats, mm_feats)
+            ap, auc, pos = ops.ap_auc(truth, nbr=idx, nbr_val=val, nbr_labels=truth)
+            out = device_metrics(ap.cpu().numpy(), auc.cpu().numpy(), pos.cpu().numpy(), 'nn')
+        else:
+            if self.metrics == 'device' and multi_label and not self._metrics_warned:
+                self._metrics_warned = True
+                warnings.warn(f'nn_probe.metrics=device holds up to {ops.AP_AUC_MAX_ROWS} clips, the set has {labels.shape[0]}: '
+                              'AP / AUC run on the host')
+            preds = knn_predictions(v_feats, a_feats, mm_feats, labels)
+            out = probe_metrics(OrderedDict((m, (p.cpu().numpy(), s.cpu().numpy())) for m, (p, s) in preds.items()),
+                                labels.cpu().numpy(), multi_label)
         if self.k is not None:
-            out.update(self._vote(model, (v_feats, a_feats, mm_feats), labels, multi_label))
+            out.update(self._vote(model, (v_feats, a_feats, mm_feats), labels, multi_label, truth))
         return out
 
-    def _vote(self, model, feats, labels, multi_label):
+    def _vote(self, model, feats, labels, multi_label, truth=None):
+        """``truth``: the queries' multi-hot labels as uint8 when AP / AUC run on the device (evaluate), else None."""
         if self.bank_loader is not None:
             *bank, bank_labels = self.extract_bank(model)
         else:
-            bank, bank_labels = feats, labels                  # the eval set against itself, each query's own row excluded
+            bank, bank_labels = feats, labels if truth is None else truth      # the eval set against itself, own rows excluded
         if multi_label:
             C = labels.shape[1]
         else:
             C = int(torch.maximum(labels.max(), bank_labels.max())) + 1
+        if truth is not None:                                  # all four views in one call; [4, C] doubles and pos come back
+            scores, _ = knn_vote_scores(feats, tuple(bank), bank_labels, C, self.k, self.temperature,
+                                        exclude_self=self.bank_loader is None)
+            ap, auc, pos = ops.ap_auc(truth, scores)
+            return device_metrics(ap.cpu().numpy(), auc.cpu().numpy(), pos.cpu().numpy(), f'knn{self.k}')
         votes = knn_vote_predictions(feats, tuple(bank), bank_labels, C, self.k, self.temperature,
                                      exclude_self=self.bank_loader is None)
         return vote_metrics(OrderedDict((m, s.cpu().numpy()) for m, (s, _) in votes.items()),

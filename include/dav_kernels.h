@@ -460,6 +460,33 @@ int dav_knn_topk_wide_f32(const float* q0, const float* x0, const float* q1, con
 int dav_knn_vote_f32(const float* top_val, const int* top_idx, int V, int Nq, int kk, int k, const int* labels,
                      const uint8_t* multihot, int N, int C, const float* inv_t, int self_offset, float* scores, int* pred,
                      hipStream_t stream);
+/* The multi-label metrics of the probe (util/misc.py:312-327 / util/knn_probe.py:133-150 of the reference; csrc/probe/ap_auc.hip):
+ * per-class average precision and ROC AUC of V (1..4) score views over n rows against the multi-hot truth y (uint8 [n, C], row
+ * stride ldy >= C, nonzero = positive), as sklearn's average_precision_score / roc_auc_score (average=None) define them: scores
+ * descending, TIES GROUPED into one threshold.
+ *   ap[V, C]  fp64: sum over the thresholds t of (R_t - R_{t-1}) P_t; 0.0 for a column without a positive.
+ *   auc[V, C] fp64: the trapezoid area under the distinct-threshold ROC from (0, 0), computed as the count of (positive, negative)
+ *             pairs the score orders correctly, ties counting half, over P * Nneg: an exact integer and ONE rounding.  NaN for a
+ *             column without a positive or without a negative (where sklearn raises).
+ *   pos[C]    int32: the positives of each class.
+ * The score of (view v, row i, class c) comes in exactly one of two forms:
+ *   dense:     scores[v * score_vs + i * score_rs + c], fp32, score_rs >= C, score_vs >= 0 (elements; the [V, Nq, C] of
+ *              dav_knn_vote_f32 or a view of wider rows);
+ *   neighbour: nbr int32 [V, n], nbr_val fp32 [V, n], nbr_labels uint8 [N, C] (dense): nbr_labels[nbr[v, i], c] * nbr_val[v, i] — the
+ *              value where the label is set, zero elsewhere (whatever the value) and for an index outside [0, N).
+ * Scores are ordered through a monotone integer image of their bits, never compared as floats: -0.0 and +0.0 are ONE threshold,
+ * subnormals stay distinct from zero and from each other.  All counts are integers; the fp64 terms of the AP are added in a fixed
+ * order, so two calls on the same input agree bit for bit.  A NaN score leaves the ap / auc of its column unspecified (pos stays
+ * exact) and touches no memory outside the operands.  One workgroup holds a whole column in LDS: n <= dav_ap_auc_max_rows.
+ * The workspace holds the truth as one bit mask per class: workspace_bytes >= C * ((n + 31) / 32) * 4 (4-byte aligned;
+ * deepavfusion_amd.ops.ap_auc_workspace_bytes).  Two launches.
+ * -1: n, C or V < 1, V > 4, n > dav_ap_auc_max_rows, ldy or score_rs < C, score_vs < 0, a NULL y / ap / auc / pos, both forms or
+ * neither (any of nbr / nbr_val / nbr_labels counts as the neighbour form), the neighbour form without all three or with N < 1;
+ * -3: a NULL or short workspace; -5: scores, nbr, nbr_val, pos or the workspace not 4-byte, ap or auc not 8-byte aligned. */
+enum { dav_ap_auc_max_rows = 32768 };   /* the cap on n */
+int dav_ap_auc_f64(const uint8_t* y, long ldy, int n, int C, int V, const float* scores, long score_rs, long score_vs,
+                   const int* nbr, const float* nbr_val, const uint8_t* nbr_labels, int N, double* ap, double* auc, int* pos,
+                   void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ---- fp32-operand twins (csrc/f32_path.hip) ------------------------------------------------ */
 /* The same contracts as the bf16 entry points above with every operand, second output and intermediate in fp32 (plain
