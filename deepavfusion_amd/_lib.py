@@ -102,6 +102,9 @@ SIGNATURES = {
     'dav_frame_transform_u8': [_p, _i, _i, _i, _p, _i, _f, _f, _f, _f, _f, _f, _p, _p],
     'dav_wave_resample_tile': [_i, _i, _i],
     'dav_wave_resample': [_p, _i, _i, _i, _l, _p, _i, _i, _i, _p, _i, _p, _i, _l, _p],
+    'dav_stft_c32': [_p, _i, _i, _l, _i, _i, _p, _p, _p, _p, _l, _p],
+    'dav_istft_c32': [_p, _l, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p],
+    'dav_sep_mask_istft': [_p, _i, _i, _l, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _p],
     'dav_batch_begin': [_i],
     'dav_batch_lane': [],
     'dav_batch_region': [_i],

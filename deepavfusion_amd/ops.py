@@ -865,3 +865,114 @@ def wave_resample(wave, taps_kn, o, n, width, out_len=None, gain=None, clamp=Fal
                                              _ptr(taps_kn), o, n, width, _ptr(gain), int(bool(clamp)), _ptr(out), out_len,
                                              out.stride(0) if B > 1 else out_len, _stream()), 'dav_wave_resample')
     return out
+
+
+# ---- source-separation audio (csrc/sep/stft.hip) ----------------------------------------------------------------------------
+
+STFT_FRAMES = 8      # dav_stft_frames of include/dav_kernels.h: frames one workgroup of dav_stft_c32 owns
+ISTFT_FRAMES = 12    # dav_istft_frames: frames one workgroup of dav_istft_c32 / dav_sep_mask_istft holds, halo included
+
+
+def istft_tile(n_fft, hop):
+    """Output samples one workgroup of the inverse owns: hop * (ISTFT_FRAMES - 2 h - 1), h = (n_fft / 2 - 1) / hop frames of
+    halo on each side (the formula of include/dav_kernels.h): outputs j and j + 1 with (j + 1) % tile == 0 come from different
+    workgroups.  0 for a geometry the kernels refuse."""
+    n_fft, hop = int(n_fft), int(hop)
+    if n_fft < 2 or n_fft % 2 or hop < 1:
+        return 0
+    return hop * max(ISTFT_FRAMES - 2 * ((n_fft // 2 - 1) // hop) - 1, 0)
+
+
+def _sep_tables(n_fft, dev, *tables):
+    for t in tables:
+        if t.dtype != F32 or tuple(t.shape) != (n_fft,) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f'the window and the cos / sin tables are dense fp32 [{n_fft}] on the operands\' device')
+
+
+def _sep_waves(wave, what):
+    if not wave.is_cuda:
+        raise RuntimeError(f'{what} runs on an MI355X (cuda) device; there is no CPU fallback')
+    if wave.dtype != F32 or wave.dim() != 2 or wave.stride(1) != 1:
+        raise ValueError(f'{what} needs fp32 waveforms [B, S] with unit stride along S')
+    return wave.shape
+
+
+def stft(wave, window, cos_tab, sin_tab, n_fft, hop, out=None):
+    """torch.stft(center=True, pad_mode='reflect', onesided=True, normalized=False, return_complex=True) with the caller's window
+    of n_fft samples (dav_stft_c32).  wave fp32 [B, S] on the device, unit stride along S (rows may be strided) -> complex64
+    [B, n_fft / 2 + 1, S / hop + 1].  ``out``: the fp32 view [B * n_freqs, 2 * frames] of such a result (re / im interleaved) with
+    unit column stride and an even row stride; it is returned in place of the complex tensor."""
+    B, S = _sep_waves(wave, 'stft')
+    n_fft, hop = int(n_fft), int(hop)
+    _sep_tables(n_fft, wave.device, window, cos_tab, sin_tab)
+    n_freqs, frames = n_fft // 2 + 1, S // max(hop, 1) + 1
+    if out is None:
+        ret = torch.empty(B, n_freqs, frames, dtype=torch.complex64, device=wave.device)
+        fl = torch.view_as_real(ret).view(B * n_freqs, 2 * frames)
+    else:
+        ret = fl = out
+        if fl.dtype != F32 or tuple(fl.shape) != (B * n_freqs, 2 * frames) or fl.stride(1) != 1 or fl.stride(0) % 2 or fl.device != wave.device:
+            raise ValueError(f'stft writes the fp32 view [{B * n_freqs}, {2 * frames}] of a complex64 result, rows an even stride apart')
+    _lib.check(_lib.load().dav_stft_c32(_ptr(wave), B, S, wave.stride(0) if B > 1 else S, n_fft, hop, _ptr(window), _ptr(cos_tab),
+                                        _ptr(sin_tab), _ptr(fl), fl.stride(0) // 2, _stream()), 'dav_stft_c32')
+    return ret
+
+
+def istft(spec, window, cos_tab, sin_tab, n_fft, hop, out=None):
+    """torch.istft(center=True, normalized=False, onesided=True, length=None) with the caller's window (dav_istft_c32).  spec
+    complex64 [B, n_fft / 2 + 1, frames] on the device with unit stride along the frames (bin rows may be strided, batch elements
+    lie n_freqs rows apart) -> fp32 [B, hop * (frames - 1)]; ``out``: such a view with unit stride along its rows."""
+    if not spec.is_cuda:
+        raise RuntimeError('istft runs on an MI355X (cuda) device; there is no CPU fallback')
+    n_fft, hop = int(n_fft), int(hop)
+    n_freqs = n_fft // 2 + 1
+    if spec.dtype != torch.complex64 or spec.dim() != 3 or spec.shape[1] != n_freqs:
+        raise ValueError(f'istft needs a complex64 spectrum [B, {n_freqs}, frames]')
+    B, _, frames = spec.shape
+    rs = spec.stride(1) if n_freqs > 1 else frames
+    if spec.stride(2) != 1 or rs < frames or (B > 1 and spec.stride(0) != n_freqs * rs):
+        raise ValueError('istft needs unit stride along the frames and batch elements n_freqs bin rows apart')
+    _sep_tables(n_fft, spec.device, window, cos_tab, sin_tab)
+    L = hop * (frames - 1)
+    if out is None:
+        out = torch.empty(B, max(L, 0), dtype=F32, device=spec.device)
+    elif out.dtype != F32 or tuple(out.shape) != (B, L) or out.stride(1) != 1 or out.device != spec.device:
+        raise ValueError(f'istft writes fp32 [{B}, {L}] with unit stride along its rows')
+    _lib.check(_lib.load().dav_istft_c32(_ptr(torch.view_as_real(spec)), rs, B, frames, n_fft, hop, _ptr(window), _ptr(cos_tab),
+                                         _ptr(sin_tab), _ptr(out), out.stride(0) if B > 1 else L, _stream()), 'dav_istft_c32')
+    return out
+
+
+def sep_mask_istft(wave, logits, window, cos_tab, sin_tab, fbank, band_lo, band_hi, n_fft, hop, out=None):
+    """The reference's SpectrogramMasking (eval_avsrcsep.py:272-277) for K masks per mixture in one launch (dav_sep_mask_istft):
+    istft(einsum('bmt,fm->bft', cat(sigmoid(logits), 0), fbank) * stft(wave)).  wave fp32 [B, S] with unit stride along S, logits
+    fp32 [B, K, n_mels, T] dense with T + 1 == S / hop + 1, fbank fp32 [n_freqs, n_mels] dense with band_lo / band_hi int32
+    [n_mels] (MelSpectrogram's buffers) -> fp32 [B, K, hop * T]; ``out``: an fp32 view [B * K, hop * T] with unit stride along its
+    rows (returned as it is)."""
+    B, S = _sep_waves(wave, 'sep_mask_istft')
+    n_fft, hop = int(n_fft), int(hop)
+    n_freqs = n_fft // 2 + 1
+    dev = wave.device
+    if logits.dtype != F32 or logits.dim() != 4 or logits.shape[0] != B or not logits.is_contiguous() or logits.device != dev:
+        raise ValueError(f'sep_mask_istft needs dense fp32 mask logits [{B}, K, n_mels, T] on the waveforms\' device')
+    _, K, n_mels, T = logits.shape
+    if T + 1 != S // max(hop, 1) + 1:
+        raise ValueError(f'sep_mask_istft: {T} mask frames for {S // max(hop, 1) + 1} STFT frames (the last frame\'s mask is the appended zero column: T + 1 == frames)')
+    _sep_tables(n_fft, dev, window, cos_tab, sin_tab)
+    if fbank.dtype != F32 or tuple(fbank.shape) != (n_freqs, n_mels) or not fbank.is_contiguous() or fbank.device != dev:
+        raise ValueError(f'sep_mask_istft needs the dense fp32 filterbank [{n_freqs}, {n_mels}]')
+    for t in (band_lo, band_hi):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n_mels,) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f'sep_mask_istft needs dense int32 band_lo / band_hi [{n_mels}]')
+    L = hop * T
+    if out is None:
+        ret = torch.empty(B, K, L, dtype=F32, device=dev)
+        rows = ret.view(B * K, L)
+    else:
+        ret = rows = out
+        if rows.dtype != F32 or tuple(rows.shape) != (B * K, L) or rows.stride(1) != 1 or rows.device != dev:
+            raise ValueError(f'sep_mask_istft writes fp32 [{B * K}, {L}] with unit stride along its rows')
+    _lib.check(_lib.load().dav_sep_mask_istft(_ptr(wave), B, S, wave.stride(0) if B > 1 else S, _ptr(logits), K, n_mels, T, n_fft, hop,
+                                              _ptr(window), _ptr(cos_tab), _ptr(sin_tab), _ptr(fbank), _ptr(band_lo), _ptr(band_hi),
+                                              _ptr(rows), rows.stride(0) if B * K > 1 else L, _stream()), 'dav_sep_mask_istft')
+    return ret

@@ -8,7 +8,9 @@ works on a batch of waveforms [B, S] (or [B, 1, S] / [1, S]) resident on the dev
 ``LogMelSpectrogram`` is the fused form (one kernel, incl. the ``[:, :, :-1]`` of datasets.py:242).
 Pad / RandomVol are index / scale plumbing (torch); the STFT, mel projection and log run in csrc/mel.hip.
 ``Resample`` is the sinc resampler the reference's loader applies to every track (datasets.py:176-181), in csrc/data/resample.hip;
-``PrepareWaveform`` is Resample -> Pad -> RandomVol in that kernel's one launch (data.audio_resample=gpu)."""
+``PrepareWaveform`` is Resample -> Pad -> RandomVol in that kernel's one launch (data.audio_resample=gpu).
+``Spectrogram(power=None)`` / ``InverseSpectrogram`` are the complex STFT and its inverse that the reference's source-separation
+evaluation composes (eval_avsrcsep.py:268-269), in csrc/sep/stft.hip; util/separation.py holds the fused masking chain."""
 import math
 import random
 
@@ -196,14 +198,11 @@ class MelSpectrogram(torch.nn.Module):
         super().__init__()
         self.sample_rate, self.n_fft, self.hop, self.n_mels = sample_rate, n_fft, hop_length or n_fft // 2, n_mels
         self.log_eps, self.drop_last = log_eps, drop_last
-        n = np.arange(n_fft, dtype=np.float64)
         fb = _fbank_htk(n_fft // 2 + 1, f_min, f_max if f_max is not None else sample_rate / 2.0, n_mels, sample_rate)
         nz = fb > 0
         lo = np.where(nz.any(0), nz.argmax(0), 0).astype(np.int32)
         hi = np.where(nz.any(0), fb.shape[0] - nz[::-1].argmax(0), 0).astype(np.int32)
-        self.register_buffer('window', torch.from_numpy(0.5 - 0.5 * np.cos(2.0 * math.pi * n / n_fft)).float(), persistent=False)
-        self.register_buffer('cos_tab', torch.from_numpy(np.cos(2.0 * math.pi * n / n_fft)).float(), persistent=False)
-        self.register_buffer('sin_tab', torch.from_numpy(np.sin(2.0 * math.pi * n / n_fft)).float(), persistent=False)
+        _register_dft_tables(self, n_fft)
         self.register_buffer('fbank', torch.from_numpy(fb).float().contiguous(), persistent=False)
         self.register_buffer('band_lo', torch.from_numpy(lo), persistent=False)
         self.register_buffer('band_hi', torch.from_numpy(hi), persistent=False)
@@ -226,6 +225,94 @@ class MelSpectrogram(torch.nn.Module):
                                   float(self.log_eps if self.log_eps is not None else 0.0), int(self.log_eps is not None),
                                   int(self.drop_last), _ptr(out), _stream()), 'dav_logmel')
         return out
+
+
+def _register_dft_tables(module, n_fft):
+    """the periodic Hann window and the exact cos / sin tables of the DFT kernels, float64 values held in fp32 — MelSpectrogram's"""
+    n = np.arange(n_fft, dtype=np.float64)
+    module.register_buffer('window', torch.from_numpy(0.5 - 0.5 * np.cos(2.0 * math.pi * n / n_fft)).float(), persistent=False)
+    module.register_buffer('cos_tab', torch.from_numpy(np.cos(2.0 * math.pi * n / n_fft)).float(), persistent=False)
+    module.register_buffer('sin_tab', torch.from_numpy(np.sin(2.0 * math.pi * n / n_fft)).float(), persistent=False)
+
+
+def _spec_geometry(n_fft, hop_length):
+    n_fft = int(n_fft)
+    hop = int(hop_length) if hop_length is not None else n_fft // 2          # torchaudio: win_length = n_fft, hop = win_length // 2
+    if n_fft < 2 or n_fft % 2 or hop < 1:
+        raise ValueError(f'n_fft={n_fft}, hop_length={hop}: the DFT kernels take an even n_fft and a positive hop')
+    return n_fft, hop
+
+
+class Spectrogram(torch.nn.Module):
+    """torchaudio.transforms.Spectrogram(n_fft, hop_length=…, power=None) with its defaults (win_length = n_fft, periodic Hann,
+    centre / reflect padding, one-sided, not normalised) — the complex STFT of eval_avsrcsep.py:268 — on dav_stft_c32:
+    waveforms [..., S] on the device -> complex64 [..., n_fft / 2 + 1, S / hop + 1].  Only ``power=None``: the power
+    spectrogram exists on the device as MelSpectrogram's first stage and is not exported on its own."""
+
+    def __init__(self, n_fft=400, hop_length=None, power=2.0):
+        super().__init__()
+        if power is not None:
+            raise ValueError(f'Spectrogram(power={power}): only power=None (the complex STFT) is on the MI355X path; the power '
+                             'spectrogram is the first stage of MelSpectrogram')
+        self.n_fft, self.hop = _spec_geometry(n_fft, hop_length)
+        self.power = None
+        _register_dft_tables(self, self.n_fft)
+
+    def forward(self, waveform):
+        if not waveform.is_cuda:
+            raise RuntimeError('the STFT runs on an MI355X (cuda) device; there is no CPU fallback')
+        from ..ops import stft
+        x = waveform.to(torch.float32)
+        x = x.reshape(-1, x.shape[-1])
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        if self.window.device != x.device:
+            self.to(x.device)
+        spec = stft(x, self.window, self.cos_tab, self.sin_tab, self.n_fft, self.hop)
+        return spec.view(*waveform.shape[:-1], *spec.shape[1:])
+
+
+def istft_envelope(n_fft, hop, frames):
+    """sum_t w[p - t hop]^2 of the periodic Hann window over ``frames`` frames, trimmed by n_fft / 2 at each end (float64):
+    what torch.istft divides by, [hop * (frames - 1)]"""
+    w2 = (0.5 - 0.5 * np.cos(2.0 * math.pi * np.arange(n_fft, dtype=np.float64) / n_fft)) ** 2
+    env = np.zeros(hop * (frames - 1) + n_fft)
+    for t in range(frames):
+        env[t * hop:t * hop + n_fft] += w2
+    return env[n_fft // 2:n_fft // 2 + hop * (frames - 1)]
+
+
+class InverseSpectrogram(torch.nn.Module):
+    """torchaudio.transforms.InverseSpectrogram(n_fft, hop_length=…) with its defaults — torch.istft(center=True,
+    normalized=False, onesided=True), eval_avsrcsep.py:269 — on dav_istft_c32: complex64 [..., n_fft / 2 + 1, frames] on the
+    device -> fp32 [..., hop * (frames - 1)].  ``length`` is not supported (the reference never passes one).  The constructor
+    makes torch's NOLA check once for the geometry: the envelope of the overlapped squared windows, trimmed, must stay above
+    1e-11 (its interior is periodic in hop, so the frames a full window spans decide it for every length)."""
+
+    def __init__(self, n_fft=400, hop_length=None):
+        super().__init__()
+        self.n_fft, self.hop = _spec_geometry(n_fft, hop_length)
+        env = istft_envelope(self.n_fft, self.hop, 2 * (-(-self.n_fft // self.hop)) + 2)
+        two = istft_envelope(self.n_fft, self.hop, 2)                        # the shortest signal: both ends at once
+        self.envelope_min = float(min(env.min(), two.min()))
+        if not self.envelope_min > 1e-11:
+            raise ValueError(f'InverseSpectrogram(n_fft={self.n_fft}, hop_length={self.hop}): the window overlap-add envelope '
+                             f'reaches {self.envelope_min:.3g} (torch.istft: "window overlap add min" must exceed 1e-11)')
+        _register_dft_tables(self, self.n_fft)
+
+    def forward(self, spec, length=None):
+        if length is not None:
+            raise ValueError('InverseSpectrogram: length is not supported; the output has hop * (frames - 1) samples')
+        if not spec.is_cuda:
+            raise RuntimeError('the inverse STFT runs on an MI355X (cuda) device; there is no CPU fallback')
+        from ..ops import istft
+        if spec.dtype != torch.complex64:
+            spec = spec.to(torch.complex64)
+        x = spec.reshape(-1, *spec.shape[-2:]).contiguous()
+        if self.window.device != x.device:
+            self.to(x.device)
+        y = istft(x, self.window, self.cos_tab, self.sin_tab, self.n_fft, self.hop)
+        return y.view(*spec.shape[:-2], y.shape[-1])
 
 
 class Log(torch.nn.Module):

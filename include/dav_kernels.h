@@ -411,6 +411,48 @@ int dav_wave_resample_tile(int o, int n, int width);
 int dav_wave_resample(const void* wave, int wave_is_i16, int B, int L, long in_rs, const float* taps_kn, int o, int n, int width,
                       const float* gain, int clamp, float* out, int out_len, long out_rs, hipStream_t stream);
 
+/* ---- source-separation audio (csrc/sep/stft.hip) ---------------------------------------------- */
+/* The reference's SpectrogramMasking (eval_avsrcsep.py:264-277, applied per sample and per source on the host, :245-254):
+ *   aT.Spectrogram(n_fft, hop_length, power=None) -> sigmoid(mask), one zero frame appended -> einsum('bmt,fm->bft', mask,
+ *   mel_scale.fb) -> mask * stft -> aT.InverseSpectrogram(n_fft, hop_length)  (torch.stft / torch.istft underneath).
+ * All fp32, direct DFTs with cos_tab / sin_tab[n] = cos / sin(2 pi n / n_fft) looked up at (k n) mod n_fft, window = the
+ * caller's n_fft samples (periodic Hann): the tables of dav_logmel.  n_freqs = n_fft / 2 + 1.
+ *
+ * dav_stft_c32 (:268, :273): wave [B][S] fp32, row stride wave_rs >= S -> spec [B][n_freqs][frames] interleaved re / im (torch's
+ *   complex64), frames = S / hop + 1, bin rows spec_rs >= frames COMPLEX elements apart, batch elements n_freqs * spec_rs.
+ *   Framing exactly dav_logmel's: center = True, reflect padding, one-sided, not normalised.  A workgroup owns dav_stft_frames
+ *   consecutive frames.
+ * dav_istft_c32 (:269, :276): spec as above -> out [B][hop (frames - 1)] fp32, row stride out_rs:
+ *   torch.istft(center=True, normalized=False, onesided=True, length=None).  Per frame
+ *     x[n] = (1/N) [Re X_0 + (-1)^n Re X_{N/2} + 2 sum_{k=1}^{N/2-1} (Re X_k cos(2 pi k n / N) - Im X_k sin(2 pi k n / N))]
+ *   (the imaginary parts of the DC and Nyquist bins are ignored, as irfft ignores them), times the window, overlap-added, divided
+ *   by the envelope sum w^2, n_fft / 2 samples dropped at each end.  The overlap-add is a gather: every output sample adds the
+ *   at most ceil(n_fft / hop) frames that cover it in increasing frame order; no atomics; two calls agree bit for bit.  The
+ *   envelope must be non-zero over the kept samples (torch's NOLA check; aT.InverseSpectrogram checks it) — a zero divides.
+ *   A workgroup holds dav_istft_frames frames in LDS, 2 h + 1 of them halo, h = (n_fft / 2 - 1) / hop, and owns the
+ *   hop * (dav_istft_frames - 2 h - 1) output samples they cover completely (9 hops at 800 / 250 and 400 / 125).
+ * dav_sep_mask_istft (:272-277 in one launch): wave [B][S] (the mixtures), logits [B][K][n_mels][T] dense (K >= 1 masks per
+ *   mixture), fbank [n_freqs][n_mels] with band_lo / band_hi [n_mels] as dav_logmel takes them -> out [B][K][hop (frames - 1)],
+ *   row (b, k) at (b K + k) out_rs.  Per (b, frame t): the STFT X once; per k:  M[f] = sum_m fbank[f][m] s(logit[b][k][m][t]) over
+ *   the filters m with band_lo[m] <= f < band_hi[m] in increasing m, s(x) = 1 / (1 + expf(-x)) (exactly 0 / 1 at -+100);
+ *   Y = M X; then as dav_istft_c32.  The mask of the last frame is zero (the appended column): T + 1 == frames is required.
+ *   Neither X, M nor Y is written to memory; the tiling is dav_istft_c32's (halo frames are transformed again).
+ * -1: an empty input (B, S, K, n_mels, T < 1; B or K > 65535), n_fft odd or < 2, hop <= 0, S <= n_fft / 2 (torch refuses such a
+ *     reflect pad), frames < 2, T + 1 != frames, a stride below its row, a NULL operand, a geometry with 2 h + 1 >=
+ *     dav_istft_frames or whose tile does not fit 160 KiB of LDS (both reference geometries fit: 800 / 250 takes 58 KB, 87 KB and
+ *     135 KB for the three calls, 400 / 125 half of that);
+ * -5: spec not 8-byte aligned, any other pointer not 4-byte aligned.  Sizes are judged before alignment and both before any HIP
+ * call.  No workspace. */
+enum { dav_stft_frames = 8 };      /* frames per workgroup of dav_stft_c32: frames t and t + 1 with (t + 1) % 8 == 0 meet at a seam */
+enum { dav_istft_frames = 12 };    /* frames per workgroup of the inverse, halo included: hop * (12 - 2 h - 1) samples per workgroup */
+int dav_stft_c32(const float* wave, int B, int S, long wave_rs, int n_fft, int hop, const float* window, const float* cos_tab,
+                 const float* sin_tab, float* spec, long spec_rs, hipStream_t stream);
+int dav_istft_c32(const float* spec, long spec_rs, int B, int frames, int n_fft, int hop, const float* window,
+                  const float* cos_tab, const float* sin_tab, float* out, long out_rs, hipStream_t stream);
+int dav_sep_mask_istft(const float* wave, int B, int S, long wave_rs, const float* logits, int K, int n_mels, int T, int n_fft,
+                       int hop, const float* window, const float* cos_tab, const float* sin_tab, const float* fbank,
+                       const int* band_lo, const int* band_hi, float* out, long out_rs, hipStream_t stream);
+
 /* ---- nearest-neighbour probe (csrc/probe/knn.hip) ------------------------------------------- */
 /* out[b, :] = v / max(||v||_2, 1e-12) with v = mean over l of x[b, l, :]: the x.mean(dim=1) + F.normalize(p=2, dim=1) of
  * util/knn_probe.py:102-110.  x fp32 [B, L, D] with row stride ld_row (>= D) and batch stride ld_batch (elements); out dense
